@@ -20,7 +20,14 @@ Prints ONE JSON line from rank 0 per the driver contract, including:
                  two scanned columns, timed with HIP events
                  inside the library on the launch stream
   cpu_baseline — the CPU oracle (restated reference algorithm, "port") timed
-                 on this box's host cores on a bounded sample
+                 on this box's host cores on a bounded sample; a run of its
+                 own after the timed steps, so only with --full (null in a
+                 plain run)
+
+A plain run sets up, warms up, times --steps steps and prints the line.
+--dump-outputs DIR additionally writes the result rows of the last timed step
+as DIR/col<i>.npy (see dump_outputs); the inputs are seeded, so two builds
+run with the same arguments can be compared array for array.
 """
 import argparse
 import ctypes
@@ -127,9 +134,12 @@ def build_device_chunk(enc_cols, n, torch):
         at = 0
         for e in encs:
             blob_base = e._cenc.blob
-            host = np.frombuffer(
-                ctypes.string_at(blob_base, e._cenc.blob_size), dtype=np.uint8)
-            t = torch.from_numpy(host.copy()).cuda()
+            # view of the encoder's blob, uploaded without a host-side copy
+            # (the copy to the device completes before .cuda() returns)
+            host = np.ctypeslib.as_array(
+                ctypes.cast(blob_base, ctypes.POINTER(ctypes.c_uint8)),
+                shape=(e._cenc.blob_size,))
+            t = torch.from_numpy(host).cuda()
             keep.append(t)
             for j in range(e._cenc.segment_count):
                 s = e._cenc.segments[j]
@@ -199,6 +209,102 @@ def cpu_baseline_leg(plan_f, enc_cols, n, cores, out_cap, pool_bytes=0):
     }
 
 
+DUMP_BUDGET = 48 << 20         # bytes of .npy payload per dump (hard cap 64 MB)
+
+_VALUE_DT = np.dtype([("id", "<u2"), ("type", "u1"), ("flags", "u1"),
+                      ("length", "<u4"), ("data", "<u8")])   # YtValue
+
+
+def _string_refs(rs, vals):
+    """(is_string, lengths, offsets into the rowset's string pool, pool) of
+    one string column of the rowset's YtValue view."""
+    from ytsaurus_amd._abi import VT_STRING
+    is_str = vals["type"] == VT_STRING
+    lens = np.where(is_str, vals["length"], 0).astype(np.int64)
+    pool = np.frombuffer(rs._pool, dtype=np.uint8)
+    base = ctypes.addressof(rs._pool)
+    off = np.where(is_str, vals["data"], base).astype(np.int64) - base
+    return is_str, lens, off, pool
+
+
+def _string_bytes(rs, vals):
+    """[rows, 1 + maxlen] float32: length, then the bytes zero-padded (a NULL
+    row is all NaN)."""
+    is_str, lens, off, pool = _string_refs(rs, vals)
+    at = np.arange(int(lens.max()) if len(lens) else 0, dtype=np.int64)
+    inside = at[None, :] < lens[:, None]
+    idx = np.where(inside, off[:, None] + at[None, :], 0)
+    out = np.empty((len(vals), 1 + len(at)), dtype=np.float32)
+    out[:, 0] = lens
+    out[:, 1:] = np.where(inside, pool[idx], 0)
+    out[~is_str] = np.nan
+    return out
+
+
+def _string_digest(rs, vals):
+    """uint64 per row over the string bytes, to order rows by a string key."""
+    _, lens, off, pool = _string_refs(rs, vals)
+    h = lens.astype(np.uint64)
+    for at in range(int(lens.max()) if len(lens) else 0):
+        inside = at < lens
+        b = np.where(inside, pool[np.where(inside, off + at, 0)], 0)
+        h = h * np.uint64(0x100000001B3) + b.astype(np.uint64)
+    return h
+
+
+def dump_outputs(rs, key_count, out_dir, prefix=""):
+    """Write the rowset the last timed step returned, one array per result
+    column: DIR/<prefix>col<i>.npy.
+
+    Numeric columns are float64 [rows] (NULL = NaN; int64 beyond 2^53 rounds);
+    string columns are float32 [rows, 1 + maxlen] (length, bytes). GROUP BY
+    leaves the row order open, so grouped results (key_count > 0) are put in
+    ascending key order first; ordered and ungrouped results keep theirs.
+    More than DUMP_BUDGET bytes are cut to a fixed, seeded sample of rows of
+    that canonical order."""
+    from ytsaurus_amd._abi import (VT_NULL, VT_INT64, VT_DOUBLE, VT_STRING)
+    os.makedirs(out_dir, exist_ok=True)
+    nrows, ncols = int(rs.row_count), int(rs.column_count)
+    flat = np.frombuffer(rs._buf, dtype=_VALUE_DT, count=nrows * ncols)
+    vals = flat.reshape(nrows, ncols)
+    is_string = [bool((vals["type"][:, c] == VT_STRING).any())
+                 for c in range(ncols)]
+
+    order = np.arange(nrows)
+    if key_count and nrows:
+        keys = []
+        for c in range(key_count - 1, -1, -1):      # lexsort: last is primary
+            col = vals[:, c]
+            if is_string[c]:
+                keys.append(_string_digest(rs, col))
+            else:
+                keys.append(np.where(col["type"] == VT_NULL, 0, col["data"]))
+            keys.append(col["type"])
+        order = np.lexsort(keys)
+
+    row_bytes = sum((4 * (1 + int(vals["length"][:, c].max())))
+                    if is_string[c] else 8 for c in range(ncols)) if nrows else 8
+    max_rows = max(1, DUMP_BUDGET // row_bytes)
+    if nrows > max_rows:
+        pick = np.random.default_rng(SEED).choice(nrows, max_rows, replace=False)
+        order = order[np.sort(pick)]
+
+    for c in range(ncols):
+        col = vals[order, c]
+        if is_string[c]:
+            arr = _string_bytes(rs, col)
+        else:
+            data = np.ascontiguousarray(col["data"])
+            arr = np.where(col["type"] == VT_DOUBLE, data.view(np.float64),
+                           np.where(col["type"] == VT_INT64,
+                                    data.view(np.int64).astype(np.float64),
+                                    data.astype(np.float64)))
+            arr[col["type"] == VT_NULL] = np.nan
+        np.save(os.path.join(out_dir, "%scol%d.npy" % (prefix, c)), arr)
+    log("wrote %d of %d result rows x %d columns to %s"
+        % (len(order), nrows, ncols, out_dir))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -212,10 +318,19 @@ def main():
                              "join"])
     ap.add_argument("--limit", type=int, default=1000,
                     help="topk workload: ORDER BY ... LIMIT n")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: "
+                         "the cpu_baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result rows as "
+                         "DIR/col<i>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--traffic-bytes", type=float, default=0.0,
                     help="measured per-launch HBM bytes from a rocprofv3 --pmc run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     n = int(args.rows)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -306,6 +421,10 @@ def main():
     upload_s = time.monotonic() - t0
     log("rank %d: uploaded %.2f GB encoded in %.1fs (%.1f GB/s PCIe-inclusive)"
         % (rank, enc_bytes / 1e9, upload_s, enc_bytes / 1e9 / max(upload_s, 1e-9)))
+    want_baseline = (args.full and rank == 0 and world == 1
+                     and not args.no_cpu_baseline)
+    if not want_baseline:
+        enc_cols = None     # the host copy only feeds the cpu_baseline leg
 
     main.join_dev = None
     if args.workload == "join":
@@ -474,8 +593,12 @@ def main():
         "traffic": traffic,
     }
 
+    if args.dump_outputs:
+        dump_outputs(out_rs, len(plan.keys), args.dump_outputs,
+                     prefix="rank%d_" % rank if world > 1 else "")
+
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if want_baseline:
         bl_pool = 0
         bl_cap = KEY_SPACE + 1024
         bl_cores = cores

@@ -145,6 +145,46 @@ struct SegmentOut {
     Blob blob;
 };
 
+/* value -> first-appearance id (1-based; 0 = absent) for one segment's
+ * statistics pass: open addressing over a power-of-two table kept at most
+ * half full. Same ids as a node-based map, without a heap node per value. */
+struct DistinctIds {
+    std::vector<uint64_t> keys;
+    std::vector<int32_t> ids;
+    uint64_t mask;
+    int64_t count = 0;
+
+    explicit DistinctIds(int64_t max_values)
+    {
+        uint64_t cap = 16;
+        while (cap < 2 * (uint64_t)max_values) cap <<= 1;
+        keys.resize(cap);
+        ids.assign(cap, 0);
+        mask = cap - 1;
+    }
+
+    uint64_t slot(uint64_t v) const
+    {
+        uint64_t h = v * 0x9E3779B97F4A7C15ULL;
+        h ^= h >> 32;
+        uint64_t at = h & mask;
+        while (ids[at] != 0 && keys[at] != v) at = (at + 1) & mask;
+        return at;
+    }
+
+    /* returns true when v was not present yet */
+    bool insert(uint64_t v)
+    {
+        uint64_t at = slot(v);
+        if (ids[at] != 0) return false;
+        keys[at] = v;
+        ids[at] = (int32_t)++count;
+        return true;
+    }
+
+    int id(uint64_t v) const { return ids[slot(v)]; }
+};
+
 /* One integer segment: values already zigzag/raw-encoded ("data" space),
  * nulls as bytemask. cum_row_count = column rows INCLUDING this segment
  * (the reference's RowCount_ at dump time, used only in size estimation). */
@@ -153,7 +193,7 @@ static void dump_int_segment(const uint64_t* data, const uint8_t* isnull, int64_
 {
     /* statistics — integer_column_writer.cpp:60-66 + AddValues :573-600 */
     uint64_t minv = UINT64_MAX, maxv = 0;
-    std::unordered_map<uint64_t, int> distinct;   /* value -> first-appearance id (1-based) */
+    DistinctIds distinct(n);                      /* value -> first-appearance id (1-based) */
     std::vector<uint64_t> first_order;            /* values in first-appearance order */
     int64_t run_count = 0;
     for (int64_t i = 0; i < n; i++) {
@@ -161,14 +201,13 @@ static void dump_int_segment(const uint64_t* data, const uint8_t* isnull, int64_
             uint64_t v = data[i];
             if (v < minv) minv = v;
             if (v > maxv) maxv = v;
-            auto it = distinct.emplace(v, (int)distinct.size() + 1);
-            if (it.second) first_order.push_back(v);
+            if (distinct.insert(v)) first_order.push_back(v);
         }
         if (i == 0 || isnull[i] != isnull[i - 1] || data[i] != data[i - 1]) {
             run_count++;
         }
     }
-    int64_t ndistinct = (int64_t)distinct.size();
+    int64_t ndistinct = distinct.count;
     uint64_t span = maxv - minv;   /* wraps to 1 for all-null segments, as in the reference */
 
     /* segment-size estimation — integer_column_writer.cpp:353-391 */
@@ -211,7 +250,7 @@ static void dump_int_segment(const uint64_t* data, const uint8_t* isnull, int64_
         for (uint64_t v : first_order) dict.push_back(v - minv);
         std::vector<uint64_t> ids(n);
         for (int64_t i = 0; i < n; i++) {
-            ids[i] = isnull[i] ? 0 : (uint64_t)distinct[data[i]];
+            ids[i] = isnull[i] ? 0 : (uint64_t)distinct.id(data[i]);
         }
         out->blob.pack(dict, span);
         out->blob.pack(ids, (uint64_t)ndistinct + 1);
@@ -245,7 +284,7 @@ static void dump_int_segment(const uint64_t* data, const uint8_t* isnull, int64_
         for (int64_t i = 0; i < n;) {
             int64_t j = i + 1;
             while (j < n && data[i] == data[j] && isnull[i] == isnull[j]) j++;
-            run_ids.push_back(isnull[i] ? 0 : (uint64_t)distinct[data[i]]);
+            run_ids.push_back(isnull[i] ? 0 : (uint64_t)distinct.id(data[i]));
             run_starts.push_back((uint64_t)i);
             i = j;
         }
