@@ -436,6 +436,20 @@ int yt_gpu_query_execute(
     YtStatistics* stats,
     char* errbuf, size_t errlen);
 
+/* Diagnostic only: YT_SCAN_PATH_* bits of the calling thread's last grouped scan. */
+enum {
+    YT_SCAN_PATH_PARTITIONED = 1 << 0,  /* partitioned group-by attempted */
+    YT_SCAN_PATH_DIRECT      = 1 << 1,  /* direct-span phase B chosen */
+    YT_SCAN_PATH_PACKED      = 1 << 2,  /* 8-byte packed records */
+    YT_SCAN_PATH_NULL_STREAM = 1 << 3,  /* second record stream for null values */
+    YT_SCAN_PATH_KEY_EXACT   = 1 << 4,  /* exact key-range scan ran */
+    YT_SCAN_PATH_VAL_EXACT   = 1 << 5,  /* exact value-range scan ran */
+    YT_SCAN_PATH_HASH_RETRY  = 1 << 6,  /* hash-partitioned retry ran */
+    YT_SCAN_PATH_FAST        = 1 << 7,  /* finished on the direct-table fast kernel */
+    YT_SCAN_PATH_GENERIC     = 1 << 8,  /* finished on the generic kernel */
+};
+uint32_t yt_gpu_debug_last_scan_path(void);
+
 /* Two-phase (coordinated) path, mirroring the bottom/front query split
  * (engine_api/coordinator.h:26,78,89; shuffle engine_api/shuffling_reader.cpp:21-88).
  *

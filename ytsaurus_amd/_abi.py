@@ -52,6 +52,17 @@ AGG_MAX = 3
 AGG_FIRST = 4
 AGG_AVG = 5
 
+# yt_gpu_debug_last_scan_path bits (diagnostic)
+SCAN_PATH_PARTITIONED = 1 << 0
+SCAN_PATH_DIRECT = 1 << 1
+SCAN_PATH_PACKED = 1 << 2
+SCAN_PATH_NULL_STREAM = 1 << 3
+SCAN_PATH_KEY_EXACT = 1 << 4
+SCAN_PATH_VAL_EXACT = 1 << 5
+SCAN_PATH_HASH_RETRY = 1 << 6
+SCAN_PATH_FAST = 1 << 7
+SCAN_PATH_GENERIC = 1 << 8
+
 
 class YtValueData(C.Union):
     _fields_ = [("i64", C.c_int64), ("u64", C.c_uint64),
@@ -224,6 +235,7 @@ def gpu_lib():
         _sig(lib, "yt_gpu_query_execute", C.c_int,
              [C.POINTER(YtPlan), C.POINTER(YtChunk), C.POINTER(YtExecOptions),
               C.POINTER(YtRowset), C.POINTER(YtStatistics), C.c_char_p, C.c_size_t])
+        _sig(lib, "yt_gpu_debug_last_scan_path", C.c_uint32, [])
         _sig(lib, "yt_gpu_query_partial", C.c_int,
              [C.POINTER(YtPlan), C.POINTER(YtChunk), C.POINTER(YtExecOptions),
               C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),

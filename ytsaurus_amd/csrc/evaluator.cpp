@@ -788,6 +788,15 @@ struct DeviceRun {
     }
 };
 
+/* diagnostic: which scan path the last grouped scan on this thread took
+ * (YT_SCAN_PATH_* bits); written by run_partitioned / run_scan only */
+static thread_local uint32_t t_last_scan_path = 0;
+
+extern "C" uint32_t yt_gpu_debug_last_scan_path(void)
+{
+    return t_last_scan_path;
+}
+
 static uint64_t next_pow2(uint64_t x)
 {
     uint64_t p = 1;
@@ -937,6 +946,8 @@ static int run_partitioned(const YtPlan* plan, const YtChunk* chunk,
     int rc = YT_OK;
     *done = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
+    uint32_t path = YT_SCAN_PATH_PARTITIONED
+                  | (force_hash ? YT_SCAN_PATH_HASH_RETRY : 0);
 
     PartParams pp;
     memset(&pp, 0, sizeof(pp));
@@ -1012,20 +1023,27 @@ static int run_partitioned(const YtPlan* plan, const YtChunk* chunk,
         if ((bk >= 1 && bk <= 23) && !(bk <= 22 && bk + bv <= 63)) {
             rc = exact_range(fs->key_col);
             if (rc != YT_OK) return rc;
+            path |= YT_SCAN_PATH_KEY_EXACT;
             span_k = R->col_zzmax[fs->key_col] - R->col_zzmin[fs->key_col];
             bk = bits_of(span_k);
         }
         if (pp.val_idx >= 0 && bk + bv >= 64 && bk + bv <= 65) {
             rc = exact_range(fs->sum_col[0]);
             if (rc != YT_OK) return rc;
+            path |= YT_SCAN_PATH_VAL_EXACT;
             uint64_t span_v = R->col_zzmax[fs->sum_col[0]] - R->col_zzmin[fs->sum_col[0]];
             bv = bits_of(span_v);
             gmin_v = R->col_zzmin[fs->sum_col[0]];
         }
-        if (bk + bv <= 64) {
+        /* a 64-bit key span beside a sum (bv is 0 then: one constant value)
+         * would make bits_k 64, and the kernels shift the value by bits_k —
+         * no valid shift count; such a plan keeps 16-byte records */
+        if (bk + bv <= 64 && !(bk == 64 && pp.val_idx >= 0)) {
             pp.packed_mode = 1;
             pp.bits_k = bk ? bk : 1;
-            if (pp.bits_k + bv > 64) pp.bits_k = bk;  /* bk>=1 here */
+            /* only bk == 0 with bv == 64 gets here (one distinct key, full-
+             * range values): the key then takes no record bits at all */
+            if (pp.bits_k + bv > 64) pp.bits_k = bk;
             pp.gmin_k = R->col_zzmin[fs->key_col];
             pp.gmin_v = gmin_v;
         }
@@ -1063,6 +1081,11 @@ static int run_partitioned(const YtPlan* plan, const YtChunk* chunk,
             pp.dshift = bk > 10 ? bk - 10 : 0;
             if (tried_direct) *tried_direct = true;
         }
+        if (pp.direct_mode) path |= YT_SCAN_PATH_DIRECT;
+        if (pp.packed_mode) path |= YT_SCAN_PATH_PACKED;
+        if (pp.has_val_nulls) path |= YT_SCAN_PATH_NULL_STREAM;
+        /* a hash retry keeps what the direct-span attempt recorded */
+        t_last_scan_path = (force_hash ? t_last_scan_path : 0) | path;
     }
 
     int64_t rows = chunk->row_count;
@@ -1250,9 +1273,11 @@ static int run_scan(const YtPlan* plan, const YtChunk* chunk,
 {
     int rc = YT_OK;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool partitioned = false;
 
     if (fs->valid && fs->key_col >= 0 && fs->nsum <= 1) {
         bool done = false;
+        partitioned = true;
         bool tried_direct = false;
         rc = run_partitioned(plan, chunk, options, R, fs, maxw, stats, &done,
                              0, &tried_direct, errbuf, errlen);
@@ -1267,6 +1292,9 @@ static int run_scan(const YtPlan* plan, const YtChunk* chunk,
         if (done) return YT_OK;
         /* else: capacity guard tripped — fall through to the direct path */
     }
+
+    t_last_scan_path = (partitioned ? t_last_scan_path : 0)
+        | (fs->valid ? YT_SCAN_PATH_FAST : YT_SCAN_PATH_GENERIC);
 
     rc = ensure_slots(R, plan->agg_count, errbuf, errlen);
     if (rc != YT_OK) return rc;

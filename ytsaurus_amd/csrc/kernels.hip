@@ -808,6 +808,16 @@ __device__ __forceinline__ void agg_update_slot(unsigned long long* aggp,
     atomicAdd(aggp + 1, 1ULL);
 }
 
+/* group-row-limit mark (overflow = 2, incomplete output). It must never
+ * replace a capacity mark (overflow = 1), on which the host discards the
+ * table and re-runs: a plain store of 2 after a 1 would pass a partial
+ * table off as a finished one. */
+__device__ __forceinline__ void mark_group_limit(TableHdr* th)
+{
+    if (th->overflow == 0)
+        atomicCAS((unsigned long long*)&th->overflow, 0ULL, 2ULL);
+}
+
 /* returns pointer to slot (stride u64s) for key, claiming if new; nullptr on
  * overflow. side groups handled by caller. */
 __device__ unsigned long long* table_probe(TableHdr* th, unsigned long long* slots,
@@ -828,7 +838,7 @@ __device__ unsigned long long* table_probe(TableHdr* th, unsigned long long* slo
         if (old == 0ULL) {
             unsigned long long ticket = atomicAdd(&th->ngroups, 1ULL);
             if (th->group_limit > 0 && (int64_t)ticket >= th->group_limit) {
-                th->overflow = 2;   /* group row limit — incomplete output */
+                mark_group_limit(th);   /* group row limit — incomplete output */
             }
             return slot;
         }
@@ -2223,6 +2233,14 @@ k_bucket_agg(const ulonglong2* recs, const unsigned long long* cursors,
     const int tid = threadIdx.x;
     const int bucket = blockIdx.x;
 
+    /* a capacity guard tripped in phase A: its cursors then count records
+     * that were never written and run past their regions, and the host
+     * discards this pass anyway — read nothing */
+    __shared__ int skip;
+    if (tid == 0) skip = (th->overflow == 1);
+    __syncthreads();
+    if (skip) return;
+
     for (int i = tid; i < kHSlots; i += 256) {
         tab[i * 3] = kEmptyKey;
         tab[i * 3 + 1] = 0;
@@ -2345,7 +2363,7 @@ k_bucket_agg(const ulonglong2* recs, const unsigned long long* cursors,
         if (key == (unsigned long long)kEmptyKey) continue;
         unsigned long long idx = atomicAdd(out_counter, 1ULL);
         unsigned long long t = atomicAdd(&th->ngroups, 1ULL);
-        if (th->group_limit > 0 && (int64_t)t >= th->group_limit) th->overflow = 2;
+        if (th->group_limit > 0 && (int64_t)t >= th->group_limit) mark_group_limit(th);
         if ((int64_t)idx >= out_cap) { th->overflow = 1; continue; }
         OutGroup& g = out[idx];
         g.key_bits = key;
@@ -2390,6 +2408,16 @@ k_bucket_agg_direct(const ulonglong2* recs, const unsigned long long* cursors,
     unsigned long long* sums = cntnn + SL;
     const int tid = threadIdx.x;
     const int bucket = blockIdx.x;
+
+    /* a capacity guard tripped in phase A: its cursors then count records
+     * that were never written and run past their regions, and the host
+     * discards this pass anyway — read nothing. The flag goes through
+     * cntnn[0] (the launch sizes the LDS for the table alone). */
+    if (tid == 0) cntnn[0] = (th->overflow == 1);
+    __syncthreads();
+    const bool skip = cntnn[0] != 0;
+    __syncthreads();
+    if (skip) return;
 
     for (int i = tid; i < SL; i += 256) { cntnn[i] = 0; sums[i] = 0; }
     __syncthreads();
@@ -2473,7 +2501,7 @@ k_bucket_agg_direct(const ulonglong2* recs, const unsigned long long* cursors,
         if (!cn) continue;
         unsigned long long idx = atomicAdd(out_counter, 1ULL);
         unsigned long long t = atomicAdd(&th->ngroups, 1ULL);
-        if (th->group_limit > 0 && (int64_t)t >= th->group_limit) th->overflow = 2;
+        if (th->group_limit > 0 && (int64_t)t >= th->group_limit) mark_group_limit(th);
         if ((int64_t)idx >= out_cap) { th->overflow = 1; continue; }
         OutGroup& g = out[idx];
         g.key_bits = (uint64_t)zz_dec(gmin_k + base_rel + (uint64_t)i);
@@ -2868,7 +2896,7 @@ __global__ void k_strgrp_merge(const DevSeg* segs, const SegEx* segex,
                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     unsigned long long t = atomicAdd(&th->ngroups, 1ULL);
                     if (th->group_limit > 0 && (int64_t)t >= th->group_limit)
-                        th->overflow = 2;
+                        mark_group_limit(th);
                     slot = cand;
                     break;
                 }
@@ -2924,7 +2952,7 @@ __global__ void k_strgrp_merge(const DevSeg* segs, const SegEx* segex,
     if (threadIdx.x == 0 && s_claims) {
         unsigned long long t = atomicAdd(&th->ngroups, s_claims);
         if (th->group_limit > 0 && (int64_t)(t + s_claims) > th->group_limit)
-            th->overflow = 2;
+            mark_group_limit(th);
     }
 }
 
@@ -3374,7 +3402,7 @@ __global__ void k_strst_merge(const YtStateRow* states, int64_t n,
     if (threadIdx.x == 0 && s_claims) {
         unsigned long long t = atomicAdd(&th->ngroups, s_claims);
         if (th->group_limit > 0 && (int64_t)(t + s_claims) > th->group_limit)
-            th->overflow = 2;
+            mark_group_limit(th);
     }
 }
 
