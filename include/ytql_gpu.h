@@ -137,6 +137,10 @@ enum {
                              state {i64 count, arg-typed sum (int wraps,
                              double fadd)}; finalize null when count==0 else
                              double(sum)/count */
+    /* With one STRING group key every function above is available (1..4
+     * aggregates, arguments any expression over int64/uint64/double/boolean
+     * columns), beside a WHERE clause over non-string columns. A STRING
+     * column inside a filter or an aggregate argument is refused. */
 };
 
 typedef struct YtAgg {
@@ -447,6 +451,13 @@ enum {
     YT_SCAN_PATH_HASH_RETRY  = 1 << 6,  /* hash-partitioned retry ran */
     YT_SCAN_PATH_FAST        = 1 << 7,  /* finished on the direct-table fast kernel */
     YT_SCAN_PATH_GENERIC     = 1 << 8,  /* finished on the generic kernel */
+    /* one STRING group key: exactly one of these two, no other bit */
+    YT_SCAN_PATH_STR_DENSE   = 1 << 9,  /* specialised kernels: no filter, <= one
+                                           sum(int64/double column) + sum(1)s,
+                                           uniform shared segmentation, no
+                                           DirectRle key segment */
+    YT_SCAN_PATH_STR_GENERAL = 1 << 10, /* general kernels: filter, any aggregate
+                                           mix, ragged segments, DirectRle keys */
 };
 uint32_t yt_gpu_debug_last_scan_path(void);
 
@@ -544,7 +555,11 @@ int yt_gpu_merge_states_mk(
  * key_bits 0 and meta bit0 set. The caller exchanges BOTH buffers (counts
  * and byte counts returned per partition); the receiver concatenates its
  * received slices in a fixed segment order and hands the extents to the
- * merge. */
+ * merge.
+ * The bottom query honours plan->filter and reads every key layout and
+ * segmentation the single-pass string GROUP BY reads. The state row carries
+ * one sum and the row count: aggregates are at most one sum (int64 or
+ * double result) plus sum(1)s; min/max/avg/first are refused here. */
 int yt_gpu_query_partial_str(
     const YtPlan* plan, const YtChunk* chunk, const YtExecOptions* options,
     int32_t partition_count, void* states_device, int64_t capacity_rows,

@@ -62,6 +62,8 @@ SCAN_PATH_VAL_EXACT = 1 << 5
 SCAN_PATH_HASH_RETRY = 1 << 6
 SCAN_PATH_FAST = 1 << 7
 SCAN_PATH_GENERIC = 1 << 8
+SCAN_PATH_STR_DENSE = 1 << 9
+SCAN_PATH_STR_GENERAL = 1 << 10
 
 
 class YtValueData(C.Union):

@@ -368,6 +368,24 @@ struct OutStrGroup {
     uint64_t cnt_nonnull;         /* low 32 = row count, high 32 = nonnull */
 };
 
+/* general string-keyed GROUP BY (kernels.hip k_strgen_*): what the merge
+ * needs to fold one accumulator record {rows, {bits, nonnull} per agg} into
+ * a slot's record of the same layout. */
+struct StrGenAggs {
+    int32_t count;
+    int32_t func[kMaxAggs];       /* YT_AGG_* */
+    int32_t is_double[kMaxAggs];  /* sum/avg state is a double */
+};
+
+/* per-group aggregates of the general string path (device→host), index-
+ * aligned with the OutStrGroup array that carries the keys; full 64-bit
+ * counts, finalized on the host by finalize_row */
+struct OutStrAgg {
+    uint64_t cnt;
+    uint64_t agg_bits[kMaxAggs];
+    uint64_t agg_nonnull[kMaxAggs];
+};
+
 struct KernelTimes {
     float scan_ms;
     int64_t scan_launches;

@@ -126,6 +126,19 @@ hipError_t ytql_launch_strgrp_compact(const DevSeg*, const SegEx*, int,
                                       const StrSlot*, uint64_t, OutStrGroup*,
                                       unsigned long long*, char*, unsigned long long*,
                                       uint64_t, TableHdr*, hipStream_t);
+hipError_t ytql_launch_strgen_accum(const DevPlan*, const DevSeg*, const SegEx*,
+                                    const int32_t*, const int32_t*, int, int64_t,
+                                    const int64_t*, unsigned long long*,
+                                    TableHdr*, unsigned*, hipStream_t);
+hipError_t ytql_launch_strgen_merge(const DevSeg*, const SegEx*, int, int,
+                                    const int64_t*, const unsigned long long*,
+                                    const StrGenAggs*, const uint64_t*,
+                                    const uint64_t*, const ulonglong2*,
+                                    StrSlot*, uint64_t, unsigned long long*,
+                                    TableHdr*, int64_t, hipStream_t);
+hipError_t ytql_launch_strgen_gather(OutStrGroup*, int64_t,
+                                     const unsigned long long*, uint64_t, int,
+                                     OutStrAgg*, int, int, hipStream_t);
 hipError_t ytql_launch_strst_count(const OutStrGroup*, int64_t, const char*,
                                    int, unsigned long long*,
                                    unsigned long long*, hipStream_t);
@@ -355,6 +368,21 @@ static uint8_t expr_static_type(const YtExpr* e, const uint8_t* col_types)
 
 static bool expr_is_col(const YtExpr* e, int* col);
 
+/* does the expression read a STRING column? The device interpreter decodes
+ * integer, boolean and double layouts only; it would misread a string blob
+ * as packed integers. */
+static bool expr_reads_string(const YtExpr* e, const uint8_t* col_types, int ncols)
+{
+    if (!e) return false;
+    if (e->op == YT_EX_COLUMN)
+        return e->col >= 0 && e->col < ncols && col_types[e->col] == YT_VT_STRING;
+    if (e->op == YT_EX_LIT_I64 || e->op == YT_EX_LIT_NULL ||
+        e->op == YT_EX_LIT_DOUBLE)
+        return false;
+    return expr_reads_string(e->a, col_types, ncols) ||
+           (e->op != YT_EX_NOT && expr_reads_string(e->b, col_types, ncols));
+}
+
 static int build_devplan(const YtPlan* plan, const YtChunk* chunk, DevPlan* p,
                          char* errbuf, size_t errlen)
 {
@@ -435,6 +463,14 @@ static int build_devplan(const YtPlan* plan, const YtChunk* chunk, DevPlan* p,
     }
 
     int rc;
+    if (expr_reads_string(plan->filter, p->col_types, p->ncols) ||
+        (plan->key_count == 1 && plan->keys[0]->op != YT_EX_COLUMN &&
+         expr_reads_string(plan->keys[0], p->col_types, p->ncols))) {
+        set_err(errbuf, errlen,
+                "string column inside a filter or key expression: "
+                "unsupported on the GPU (no string predicates)");
+        return YT_ERR_UNSUPPORTED;
+    }
     if (plan->filter) {
         p->filter_off = p->prog_len;
         rc = compile_expr(plan->filter, p, &p->filter_len, errbuf, errlen);
@@ -474,6 +510,13 @@ static int build_devplan(const YtPlan* plan, const YtChunk* chunk, DevPlan* p,
                 set_err(errbuf, errlen, "avg: WITH TOTALS not this round");
                 return YT_ERR_UNSUPPORTED;
             }
+        }
+        if (plan->aggs[a]->func != YT_AGG_SUM1 &&
+            expr_reads_string(plan->aggs[a]->arg, p->col_types, p->ncols)) {
+            set_err(errbuf, errlen,
+                    "string column inside an aggregate argument: "
+                    "unsupported on the GPU");
+            return YT_ERR_UNSUPPORTED;
         }
         if (plan->aggs[a]->func != YT_AGG_SUM1) {
             p->agg_off[a] = p->prog_len;
@@ -2585,10 +2628,87 @@ fail:
 }
 
 
-/* string-keyed GROUP BY (config-5 family): dictionary-encoded string key,
- * aggregates {sum(col), sum(1)}. Dense per-segment id accumulators, then an
- * exact cross-segment merge (hash gate + byte compare), then device-side
- * key materialization into the caller's string pool. */
+/* general string path: emit [key(string), aggs...] rows from the compacted
+ * key refs (hgroups: pool offset|len) and their aggregate records (haggs),
+ * then the null-key side group; aggregates finalize through finalize_row
+ * exactly as on the int-key paths. */
+static int emit_string_general(const YtPlan* plan, const uint8_t* sum_type,
+                               const OutStrGroup* hgroups,
+                               const OutStrAgg* haggs, int64_t ngroups,
+                               const char* pool, const TableHdr& th,
+                               int64_t output_row_limit, int* out_limited,
+                               YtRowset* output, char* errbuf, size_t errlen)
+{
+    const int ncols = 1 + plan->agg_count;
+    uint8_t st[kMaxAggs];
+    memcpy(st, sum_type, sizeof(st));
+    for (int64_t gI = 0; gI < ngroups + 1; gI++) {
+        const int knull = gI == ngroups;
+        if (knull && !th.side_used[1]) break;
+        if (output_row_limit > 0 && output->row_count >= output_row_limit) {
+            *out_limited = 1;
+            break;
+        }
+        if (output->row_count >= output->capacity_rows) {
+            set_err(errbuf, errlen, "rowset too small");
+            return YT_ERR_CAPACITY;
+        }
+        YtValue* dst = output->values + output->row_count * ncols;
+        HVal row[kMaxAggs];
+        int nrow = 0;
+        if (knull) {
+            /* side_agg interleaves {bits, nonnull} per aggregate */
+            uint64_t ab[kMaxAggs], an[kMaxAggs];
+            for (int a = 0; a < plan->agg_count; a++) {
+                ab[a] = th.side_agg[1][2 * a];
+                an[a] = th.side_agg[1][2 * a + 1];
+            }
+            finalize_row(plan, YT_VT_STRING, st, 0, 1, th.side_cnt[1], ab, an,
+                         row, &nrow, 0);
+            dst[0].type = YT_VT_NULL;
+            dst[0].length = 0;
+            dst[0].data.bits = 0;
+        } else {
+            const OutStrGroup& g = hgroups[gI];
+            const uint32_t klen = (uint32_t)(g.off_len & 0xFFFFFF);
+            finalize_row(plan, YT_VT_STRING, st, 0, 0, haggs[gI].cnt,
+                         haggs[gI].agg_bits, haggs[gI].agg_nonnull, row, &nrow, 0);
+            if (output->string_pool_used + klen > output->string_pool_capacity) {
+                set_err(errbuf, errlen, "string pool too small");
+                return YT_ERR_CAPACITY;
+            }
+            char* kdst = output->string_pool + output->string_pool_used;
+            if (klen) memcpy(kdst, pool + (g.off_len >> 24), klen);
+            dst[0].type = YT_VT_STRING;
+            dst[0].length = klen;
+            dst[0].data.str = kdst;
+            output->string_pool_used += klen;
+        }
+        dst[0].id = 0;
+        dst[0].flags = 0;
+        for (int a = 0; a < nrow; a++) {
+            YtValue& v = dst[1 + a];
+            v.id = (uint16_t)(1 + a);
+            v.type = row[a].type;
+            v.flags = 0;
+            v.length = 0;
+            v.data.bits = row[a].bits;
+        }
+        output->row_count++;
+    }
+    return YT_OK;
+}
+
+/* string-keyed GROUP BY (config-5 family). Dense per-segment dictionary-id
+ * accumulators, then an exact cross-segment merge (hash gate + byte
+ * compare), then device-side key materialization into the caller's string
+ * pool. Two kernel sets share that pipeline:
+ *  - the specialised one (YT_SCAN_PATH_STR_DENSE): no filter, at most one
+ *    sum over a plain int64/double column plus sum(1)s, uniform key
+ *    segments that the value column shares, no DirectRle key segment;
+ *  - the general one (YT_SCAN_PATH_STR_GENERAL): everything else — filter,
+ *    min/max/avg/first, expression arguments, ragged segmentation, DirectRle
+ *    keys (k_strgen_* in kernels.hip). */
 static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
                             const YtExecOptions* options, int key_col,
                             YtRowset* output, YtStatistics* stats, double tw0,
@@ -2597,30 +2717,89 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
 {
     int rc = YT_OK;
     int sum_slot = -1, sum_col = -1, val_is_double = 0;
+    bool general = plan->filter != nullptr;
+    uint8_t col_types[kMaxCols];
+    memset(col_types, YT_VT_INT64, sizeof(col_types));
+    for (int c = 0; c < chunk->column_count && c < kMaxCols; c++)
+        col_types[c] = (uint8_t)chunk->columns[c].value_type;
     for (int a = 0; a < plan->agg_count; a++) {
         int f = plan->aggs[a]->func;
         if (f == YT_AGG_SUM) {
             int c;
-            if (sum_slot >= 0 || !expr_is_col(plan->aggs[a]->arg, &c)) {
-                set_err(errbuf, errlen, "string keys: one direct sum this round");
-                return YT_ERR_UNSUPPORTED;
+            if (sum_slot >= 0) {
+                if (po) {
+                    set_err(errbuf, errlen,
+                            "partial_str: the string state row carries one sum");
+                    return YT_ERR_UNSUPPORTED;
+                }
+                general = true;
+                continue;
             }
             sum_slot = a;
-            sum_col = c;
-            val_is_double = chunk->columns[c].value_type == YT_VT_DOUBLE;
-            if (!val_is_double && chunk->columns[c].value_type != YT_VT_INT64) {
-                set_err(errbuf, errlen, "string keys: int64/double sums this round");
-                return YT_ERR_UNSUPPORTED;
+            if (expr_is_col(plan->aggs[a]->arg, &c) && c >= 0 &&
+                c < chunk->column_count && c < kMaxCols) {
+                sum_col = c;
+                val_is_double = col_types[c] == YT_VT_DOUBLE;
+                if (!val_is_double && col_types[c] != YT_VT_INT64) general = true;
+            } else {
+                general = true;     /* sum(<expression>) */
             }
         } else if (f != YT_AGG_SUM1) {
-            set_err(errbuf, errlen, "string keys: sum/sum(1) this round");
-            return YT_ERR_UNSUPPORTED;
+            if (po) {
+                set_err(errbuf, errlen,
+                        "partial_str: min/max/avg/first are not exchanged for "
+                        "string keys (the state row carries sum and sum(1))");
+                return YT_ERR_UNSUPPORTED;
+            }
+            general = true;
         }
     }
     if (plan->project_count) {
         set_err(errbuf, errlen, "string keys: no post-projection this round");
         return YT_ERR_UNSUPPORTED;
     }
+    /* key layout and segmentation decide too (host-visible segment meta) */
+    {
+        const YtColumn& kcol = chunk->columns[key_col];
+        for (int i = 0; i < kcol.segment_count; i++) {
+            if (kcol.segments[i].type == YT_SEG_DIRECT_RLE) general = true;
+            if (i + 1 < kcol.segment_count &&
+                kcol.segments[i].row_count != kcol.segments[0].row_count)
+                general = true;
+        }
+        if (!general && sum_col >= 0) {
+            const YtColumn& vcol = chunk->columns[sum_col];
+            if (vcol.segment_count != kcol.segment_count) general = true;
+            for (int i = 0; !general && i < kcol.segment_count; i++)
+                if (vcol.segments[i].row_count != kcol.segments[i].row_count)
+                    general = true;
+        }
+    }
+    DevPlan dp;
+    uint8_t sum_type[kMaxAggs];
+    if (general) {
+        /* the interpreter's plan: compiles filter + aggregate arguments and
+         * carries its refusals (string columns in expressions, avg + WITH
+         * TOTALS, more than kMaxAggs aggregates, ...) */
+        rc = build_devplan(plan, chunk, &dp, errbuf, errlen);
+        if (rc) return rc;
+        for (int a = 0; a < plan->agg_count; a++) {
+            sum_type[a] = (plan->aggs[a]->func != YT_AGG_SUM1)
+                ? expr_static_type(plan->aggs[a]->arg, col_types)
+                : (uint8_t)YT_VT_INT64;
+            if (sum_type[a] == YT_VT_NULL) sum_type[a] = YT_VT_INT64;
+        }
+        if (sum_slot >= 0) {
+            val_is_double = sum_type[sum_slot] == YT_VT_DOUBLE;
+            if (po && !val_is_double && sum_type[sum_slot] != YT_VT_INT64) {
+                set_err(errbuf, errlen,
+                        "partial_str: the string state row carries an int64 "
+                        "or double sum");
+                return YT_ERR_UNSUPPORTED;
+            }
+        }
+    }
+    t_last_scan_path = general ? YT_SCAN_PATH_STR_GENERAL : YT_SCAN_PATH_STR_DENSE;
 
     DeviceRun R;
     R.stream = (hipStream_t)(uintptr_t)options->stream;
@@ -2657,22 +2836,20 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
         HIP_CHECK(hipMemcpy(ksegex.data(), R.d_segex + koff,
                             sizeof(SegEx) * knseg, hipMemcpyDeviceToHost));
         for (int i = 0; i < knseg; i++) {
-            if (!(ksegex[i].flags & (8 | 32))) {
-                set_err(errbuf, errlen,
-                        "string keys: dictionary or direct-dense segments "
-                        "(RLE strings not this round)");
+            if (!(ksegex[i].flags & (general ? (8 | 32 | 64) : (8 | 32)))) {
+                set_err(errbuf, errlen, "string keys: unknown key segment layout");
                 return YT_ERR_UNSUPPORTED;
             }
         }
         int32_t rows0 = R.h_segs[koff].row_count;
-        for (int i = 0; i + 1 < knseg; i++) {
-            if (R.h_segs[koff + i].row_count != rows0) {
-                set_err(errbuf, errlen, "string keys: non-uniform segments");
-                return YT_ERR_UNSUPPORTED;
-            }
-        }
-        if (sum_col >= 0 && R.h_cnt[sum_col] != knseg) {
-            set_err(errbuf, errlen, "string keys: column segmentation mismatch");
+        /* accumulator record: {cnt|nonnull<<32, sum} on the specialised
+         * path, {rows, {bits, nonnull} per aggregate} on the general one */
+        const int acc_stride = general ? 1 + 2 * plan->agg_count : 2;
+        /* rows actually scanned (input_row_limit clamps the segment list) */
+        const int64_t scan_rows = R.h_segs[koff + knseg - 1].start_row
+                                + R.h_segs[koff + knseg - 1].row_count;
+        if (general && po && scan_rows >= ((int64_t)1 << 32)) {
+            set_err(errbuf, errlen, "partial_str: chunk too large (2^32 rows)");
             return YT_ERR_UNSUPPORTED;
         }
 
@@ -2713,8 +2890,8 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
         HIP_CHECK(hipMemcpyAsync(d_accbase, acc_base.data(),
                                  sizeof(int64_t) * (knseg + 1),
                                  hipMemcpyHostToDevice, R.stream));
-        HIP_CHECK(pool_alloc(&d_acc, sizeof(uint64_t) * 2 * (total_dict ? total_dict : 1)));
-        HIP_CHECK(hipMemsetAsync(d_acc, 0, sizeof(uint64_t) * 2 * (total_dict ? total_dict : 1), R.stream));
+        HIP_CHECK(pool_alloc(&d_acc, sizeof(uint64_t) * acc_stride * (total_dict ? total_dict : 1)));
+        HIP_CHECK(hipMemsetAsync(d_acc, 0, sizeof(uint64_t) * acc_stride * (total_dict ? total_dict : 1), R.stream));
         HIP_CHECK(pool_alloc(&d_hashes, sizeof(uint64_t) * (total_dict ? total_dict : 1)));
         /* per-entry identity + prefix arrays: filled by the hash kernel so
          * the merge's hot path reads them as a stream (YTQL_STRMERGE=0
@@ -2751,6 +2928,23 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
         if (nslots > nslots_cap) nslots = nslots_cap;
         HIP_CHECK(pool_alloc(&d_slots, sizeof(StrSlot) * nslots));
         HIP_CHECK(hipMemsetAsync(d_slots, 0, sizeof(StrSlot) * nslots, R.stream));
+        /* general path: one aggregate record per slot, beside the slot table
+         * (the slot line itself stays 64 B) */
+        unsigned long long* d_slotaggs = nullptr;
+        OutStrAgg* d_oaggs = nullptr;
+        OutStrAgg* haggs = nullptr;
+        StrGenAggs ag;
+        memset(&ag, 0, sizeof(ag));
+        if (general) {
+            ag.count = plan->agg_count;
+            for (int a = 0; a < plan->agg_count; a++) {
+                ag.func[a] = plan->aggs[a]->func;
+                ag.is_double[a] = sum_type[a] == YT_VT_DOUBLE;
+            }
+            HIP_CHECK(pool_alloc(&d_slotaggs, sizeof(uint64_t) * acc_stride * nslots));
+            HIP_CHECK(hipMemsetAsync(d_slotaggs, 0,
+                                     sizeof(uint64_t) * acc_stride * nslots, R.stream));
+        }
 
         hipEvent_t e0, e1, e2, ea, eh;
         HIP_CHECK(hipEventCreate(&e0));
@@ -2759,20 +2953,35 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
         HIP_CHECK(hipEventCreate(&ea));
         HIP_CHECK(hipEventCreate(&eh));
         HIP_CHECK(hipEventRecord(e0, R.stream));
-        HIP_CHECK(ytql_launch_strgrp_accum(&sp, R.d_segs, R.d_segex, d_accbase,
-                                           d_acc, R.d_th, R.stream));
+        if (general) {
+            HIP_CHECK(ytql_launch_strgen_accum(&dp, R.d_segs, R.d_segex, R.d_off,
+                                               R.d_cnt, key_col, scan_rows,
+                                               d_accbase, d_acc, R.d_th, R.d_err,
+                                               R.stream));
+        } else {
+            HIP_CHECK(ytql_launch_strgrp_accum(&sp, R.d_segs, R.d_segex, d_accbase,
+                                               d_acc, R.d_th, R.stream));
+        }
         HIP_CHECK(hipEventRecord(ea, R.stream));
         HIP_CHECK(ytql_launch_strgrp_hash(R.d_segs, R.d_segex, koff, knseg,
                                           d_accbase, d_hashes, d_idents, d_pfxs,
                                           total_dict, R.stream));
         HIP_CHECK(hipEventRecord(eh, R.stream));
         for (;;) {
-            HIP_CHECK(ytql_launch_strgrp_merge(R.d_segs, R.d_segex, koff, knseg,
-                                               d_accbase, d_acc, d_hashes,
-                                               d_idents, d_pfxs,
-                                               d_slots, nslots, val_is_double,
-                                               merge_fast, R.d_th, total_dict,
-                                               R.stream));
+            if (general) {
+                HIP_CHECK(ytql_launch_strgen_merge(R.d_segs, R.d_segex, koff, knseg,
+                                                   d_accbase, d_acc, &ag, d_hashes,
+                                                   d_idents, d_pfxs, d_slots, nslots,
+                                                   d_slotaggs, R.d_th, total_dict,
+                                                   R.stream));
+            } else {
+                HIP_CHECK(ytql_launch_strgrp_merge(R.d_segs, R.d_segex, koff, knseg,
+                                                   d_accbase, d_acc, d_hashes,
+                                                   d_idents, d_pfxs,
+                                                   d_slots, nslots, val_is_double,
+                                                   merge_fast, R.d_th, total_dict,
+                                                   R.stream));
+            }
             HIP_CHECK(hipMemcpy(&th, R.d_th, sizeof(th), hipMemcpyDeviceToHost));
             if (th.overflow != 1 || nslots >= nslots_cap) break;
             g_pool.put(d_slots);
@@ -2780,11 +2989,35 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
             if (nslots > nslots_cap) nslots = nslots_cap;
             HIP_CHECK(pool_alloc(&d_slots, sizeof(StrSlot) * nslots));
             HIP_CHECK(hipMemsetAsync(d_slots, 0, sizeof(StrSlot) * nslots, R.stream));
+            if (general) {
+                g_pool.put(d_slotaggs);
+                d_slotaggs = nullptr;
+                HIP_CHECK(pool_alloc(&d_slotaggs, sizeof(uint64_t) * acc_stride * nslots));
+                HIP_CHECK(hipMemsetAsync(d_slotaggs, 0,
+                                         sizeof(uint64_t) * acc_stride * nslots,
+                                         R.stream));
+            }
             th.ngroups = 0;
             th.overflow = 0;
             HIP_CHECK(hipMemcpy(R.d_th, &th, sizeof(th), hipMemcpyHostToDevice));
         }
         HIP_CHECK(hipEventRecord(e1, R.stream));
+        if (general) {
+            /* expression errors raised by the accumulate kernel */
+            unsigned kerr = 0;
+            HIP_CHECK(hipMemcpy(&kerr, R.d_err, sizeof(unsigned), hipMemcpyDeviceToHost));
+            if (kerr) {
+                g_pool.put(d_accbase); g_pool.put(d_acc); g_pool.put(d_hashes);
+                g_pool.put(d_idents); g_pool.put(d_pfxs); g_pool.put(d_slots);
+                g_pool.put(d_slotaggs);
+                (void)hipEventDestroy(ea); (void)hipEventDestroy(eh);
+                (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+                (void)hipEventDestroy(e2);
+                set_err(errbuf, errlen, kerr == YT_ERR_DIV_ZERO
+                        ? "Division by zero" : "expression error");
+                return (int)kerr;
+            }
+        }
 
         /* compact + materialize keys into a device pool */
         int64_t ngroups = (int64_t)th.ngroups;
@@ -2807,6 +3040,23 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
                                                  d_pool, d_ctr + 1, pool_cap,
                                                  R.d_th, R.stream));
         }
+        if (general) {
+            /* compact copied each slot's index (left in StrSlot.sum_bits by
+             * the merge) into OutStrGroup.sum_bits: gather the aggregate
+             * records in group order. The bottom query also packs them back
+             * into the {sum, cnt|nonnull} form the partition kernels read —
+             * 32-bit halves, so it needs the chunk below 2^32 rows. */
+            HIP_CHECK(pool_alloc(&d_oaggs, sizeof(OutStrAgg) * (ngroups ? ngroups : 1)));
+            HIP_CHECK(pool_alloc_host(&haggs, sizeof(OutStrAgg) * (ngroups ? ngroups : 1)));
+            if (ngroups > 0) {
+                HIP_CHECK(ytql_launch_strgen_gather(d_out, ngroups, d_slotaggs,
+                                                    nslots, plan->agg_count,
+                                                    d_oaggs, po ? 1 : 0, sum_slot,
+                                                    R.stream));
+                HIP_CHECK(hipMemcpyAsync(haggs, d_oaggs, sizeof(OutStrAgg) * ngroups,
+                                         hipMemcpyDeviceToHost, R.stream));
+            }
+        }
         OutStrGroup* hgroups = nullptr;
         HIP_CHECK(pool_alloc_host(&hgroups,
                                   sizeof(OutStrGroup) * (ngroups ? ngroups : 1)));
@@ -2824,8 +3074,9 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
             float ms_acc = 0, ms_hash = 0;
             HIP_CHECK(hipEventElapsedTime(&ms_acc, e0, ea));
             HIP_CHECK(hipEventElapsedTime(&ms_hash, ea, eh));
-            fprintf(stderr, "[ytql timing] strgrp: accum %.2fms hash %.2fms "
+            fprintf(stderr, "[ytql timing] strgrp%s: accum %.2fms hash %.2fms "
                     "merge %.2fms compact+D2H %.2fms\n",
+                    general ? " (general)" : "",
                     ms_acc, ms_hash, ms - ms_acc - ms_hash, ms_other);
         }
         (void)hipEventDestroy(ea);
@@ -2839,6 +3090,7 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
             g_pool.put(d_idents); g_pool.put(d_pfxs);
             g_pool.put(d_slots); g_pool.put(d_out); g_pool.put(d_pool);
             g_pool.put(d_ctr); g_pool.put(hgroups);
+            g_pool.put(d_slotaggs); g_pool.put(d_oaggs); g_pool.put(haggs);
             set_err(errbuf, errlen, "string merge table/pool overflow");
             return YT_ERR_CAPACITY;
         }
@@ -2852,6 +3104,7 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
                 g_pool.put(d_idents); g_pool.put(d_pfxs);
                 g_pool.put(d_slots); g_pool.put(d_out); g_pool.put(d_pool);
                 g_pool.put(d_ctr); g_pool.put(hgroups);
+                g_pool.put(d_slotaggs); g_pool.put(d_oaggs); g_pool.put(haggs);
             };
             const int np = po->partition_count;
             const int p_null = (int)(splitmix64_host(
@@ -2946,6 +3199,20 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
         int out_limited = 0;
         int64_t ng = ngroups;
         int has_null_row = th.side_used[1] ? 1 : 0;
+        if (general) {
+            std::vector<char> pool(hctr[1] ? hctr[1] : 1);
+            if (hctr[1]) {
+                HIP_CHECK(hipMemcpy(pool.data(), d_pool, hctr[1], hipMemcpyDeviceToHost));
+            }
+            if (ngroups > 0) {
+                HIP_CHECK(hipMemcpy(hgroups, d_out, sizeof(OutStrGroup) * ngroups,
+                                    hipMemcpyDeviceToHost));
+            }
+            rc = emit_string_general(plan, sum_type, hgroups, haggs, ngroups,
+                                     pool.data(), th, options->output_row_limit,
+                                     &out_limited, output, errbuf, errlen);
+            goto emitted;
+        }
         if (options->output_row_limit == 0 &&
             ng + has_null_row <= output->capacity_rows &&
             (unsigned long long)hctr[1] <= (unsigned long long)output->string_pool_capacity &&
@@ -3191,6 +3458,7 @@ emitted:
         g_pool.put(d_idents); g_pool.put(d_pfxs);
         g_pool.put(d_slots); g_pool.put(d_out); g_pool.put(d_pool);
         g_pool.put(d_ctr); g_pool.put(hgroups);
+        g_pool.put(d_slotaggs); g_pool.put(d_oaggs); g_pool.put(haggs);
     }
     return rc;
 fail:

@@ -233,8 +233,29 @@ __global__ void k_parse_segments(const DevSeg* segs, int nsegs, SegEx* out,
             e.flags |= 32;  /* direct-dense string segment */
             break;
         }
+        case YT_SEG_DIRECT_RLE: {
+            /* [run starts][run END offsets, diff-from-expected]
+             * [run null bitmap][run data] (string_column_writer.cpp
+             * DumpDirectRleData). As a GROUP key this is an identity
+             * dictionary over RUNS: entry j = run j's string, row -> run by
+             * binary search on the starts, null runs by the bitmap (their
+             * entries are empty and their accumulators stay zero). */
+            e.w_starts = w0;
+            e.run_count = (uint32_t)n0;
+            e.off_starts_words = 1;
+            uint64_t h1 = b[words0];
+            e.w_values = (uint32_t)(h1 >> 56);
+            e.dict_size = e.run_count;
+            e.off_values_words = words0 + 1;
+            int64_t words1 = 1 + (int64_t)(((uint64_t)e.w_values * e.run_count + 63) >> 6);
+            e.off_bitmap_bytes = (words0 + words1) * 8;
+            int64_t bm = (((int64_t)e.run_count + 7) / 8 + 7) & ~(int64_t)7;
+            e.off_doubles_bytes = e.off_bitmap_bytes + bm;
+            e.flags |= 64;  /* direct-RLE string segment */
+            break;
+        }
         default:
-            e.flags |= 16;  /* RLE direct string: no GPU key path yet */
+            e.flags |= 16;  /* unknown string layout: no GPU key path */
             break;
         }
         out[i] = e;
@@ -3068,6 +3089,288 @@ __global__ void k_strgrp_compact(const DevSeg* segs, const SegEx* segex,
 }
 
 /* ------------------------------------------------------------------ */
+/* general string-keyed GROUP BY (common.h StrGenAggs): any filter, the
+ * whole aggregate family, all four key layouts, ragged segmentation. Same
+ * three stages as the specialised kernels above — dense per-(segment,
+ * dictionary id) accumulators, identity merge into StrSlot, compact — with
+ * a wider accumulator record and a per-slot aggregate array beside the
+ * slot table. k_strgrp_hash and k_strgrp_compact are shared as they are. */
+
+/* 1-based dictionary id of row j of a string key segment; 0 = null key */
+__device__ __forceinline__ uint64_t str_key_id(const DevSeg& sk, const SegEx& ek,
+                                               int64_t j)
+{
+    if (ek.flags & 32)      /* direct dense: entry j is row j */
+        return bm_get((const uint8_t*)sk.blob + ek.off_bitmap_bytes, j)
+            ? 0 : (uint64_t)(j + 1);
+    if (ek.flags & 8) {
+        const uint64_t* ids = sk.blob + ek.off_ids_words;
+        if (sk.type == YT_SEG_DICTIONARY_DENSE) return bp_get(ids, ek.w_ids, j);
+    } else if (!(ek.flags & 64)) {
+        return 0;           /* unknown layout: refused by the host */
+    }
+    /* RLE forms: the run whose start <= j (seg_value_at's search) */
+    const uint64_t* starts = sk.blob + ek.off_starts_words;
+    uint32_t lo = 0, hi = ek.run_count;
+    while (lo + 1 < hi) {
+        uint32_t mid = (lo + hi) / 2;
+        if (bp_get(starts, ek.w_starts, mid) <= (uint64_t)j) lo = mid;
+        else hi = mid;
+    }
+    if (ek.flags & 64)      /* direct RLE: entry = run, null by run bitmap */
+        return bm_get((const uint8_t*)sk.blob + ek.off_bitmap_bytes, lo)
+            ? 0 : (uint64_t)lo + 1;
+    return bp_get(sk.blob + ek.off_ids_words, ek.w_ids, lo);
+}
+
+/* G1: per row — filter, aggregate arguments (eval_prog), then
+ * agg_update_slot into the row's record
+ *   acc[stride * (acc_base[seg] + id-1)] = { rows, {bits, nonnull} per agg }
+ * with stride = 1 + 2*agg_count. Null keys go to TableHdr side group 1, as
+ * in table_update_generic. Blocks take whole 2048-row tiles so a block's
+ * atomics stay inside one key segment's accumulator region. */
+constexpr int kStrGenTile = 2048;
+
+__global__ void __launch_bounds__(256)
+k_strgen_accum(DevPlan p, const DevSeg* segs, const SegEx* segex,
+               const int32_t* col_seg_off, const int32_t* col_seg_cnt,
+               int key_col, int64_t row_count, const int64_t* acc_base,
+               unsigned long long* acc, TableHdr* th, unsigned* error_out)
+{
+    ColCtx c;
+    c.segs = segs;
+    c.segex = segex;
+    c.col_seg_off = col_seg_off;
+    c.col_seg_cnt = col_seg_cnt;
+    c.error = 0;
+    const int koff = col_seg_off[key_col];
+    const int kcnt = col_seg_cnt[key_col];
+    const int kshift = p.col_uniform_shift[key_col];
+    const int stride = 1 + 2 * p.agg_count;
+    DVal aggv[kMaxAggs];
+
+    const int64_t ntiles = (row_count + kStrGenTile - 1) / kStrGenTile;
+    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        for (int i = threadIdx.x; i < kStrGenTile; i += 256) {
+            const int64_t r = t * kStrGenTile + i;
+            if (r >= row_count) break;
+            c.row = r;
+            if (p.filter_len) {
+                DVal f = eval_prog(p, c, p.filter_off, p.filter_len);
+                if (c.error) { atomicMax(error_out, c.error); return; }
+                if (f.null_ || f.bits == 0) continue;
+            }
+            for (int a = 0; a < p.agg_count; a++) {
+                if (p.agg_func[a] != YT_AGG_SUM1)
+                    aggv[a] = eval_prog(p, c, p.agg_off[a], p.agg_len[a]);
+            }
+            if (c.error) { atomicMax(error_out, c.error); return; }
+            /* key row -> segment, the way col_value does it */
+            int ks;
+            if (kshift) {
+                ks = (int)(r >> kshift);
+            } else {
+                int hi = kcnt;
+                ks = 0;
+                while (ks + 1 < hi) {
+                    int mid = (ks + hi) / 2;
+                    if (segs[koff + mid].start_row <= r) ks = mid;
+                    else hi = mid;
+                }
+            }
+            const DevSeg& sk = segs[koff + ks];
+            const uint64_t id = str_key_id(sk, segex[koff + ks], r - sk.start_row);
+            unsigned long long* cntp;
+            unsigned long long* aggp;
+            if (id == 0) {
+                th->side_used[1] = 1;
+                cntp = (unsigned long long*)&th->side_cnt[1];
+                aggp = (unsigned long long*)&th->side_agg[1][0];
+            } else {
+                cntp = acc + (uint64_t)stride * (uint64_t)(acc_base[ks] + (int64_t)id - 1);
+                aggp = cntp + 1;
+            }
+            atomicAdd(cntp, 1ULL);
+            for (int a = 0; a < p.agg_count; a++) {
+                if (p.agg_func[a] != YT_AGG_SUM1)
+                    agg_update_slot(aggp + 2 * a, p, a, aggv[a]);
+            }
+        }
+    }
+}
+
+/* find-or-claim the merge slot of dictionary entry g: the slot identity
+ * protocol of k_strgrp_merge's streamed path (ident/pfx in-slot, exact
+ * owner-entry compare as the fallback), as a function. k_strgrp_merge keeps
+ * its own inlined copy: it is the measured config-5 hot loop and stays
+ * byte-for-byte what was tuned. Returns nullptr when the probe gave up
+ * (table too small); *claimed = 1 when this call created the group. */
+__device__ StrSlot* strgrp_find_slot(const DevSeg* segs, const SegEx* segex,
+                                     int key_seg_off, int nsegs,
+                                     const int64_t* acc_base, int64_t g,
+                                     const uint64_t* hashes,
+                                     const uint64_t* idents,
+                                     const ulonglong2* pfxs,
+                                     StrSlot* slots, uint64_t mask, int* claimed)
+{
+    const uint64_t h = hashes[g];
+    const uint64_t my_ident = idents[g];
+    const uint32_t my_len = (uint32_t)(my_ident & 0xFFFF);
+    const ulonglong2 pf = pfxs[g];
+    int lo = 0, hi = nsegs;
+    while (lo + 1 < hi) {
+        int mid = (lo + hi) / 2;
+        if (acc_base[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    const unsigned long long rep = ((unsigned long long)(lo + 1) << 32)
+                                 | (unsigned long long)(g - acc_base[lo] + 1);
+    *claimed = 0;
+    uint64_t sidx = mix64(h) & mask;
+    const uint64_t max_probe = mask < 8192 ? mask : 8192;
+    for (uint64_t it = 0; it <= max_probe; it++, sidx = (sidx + 1) & mask) {
+        StrSlot* cand = &slots[sidx];
+        unsigned long long cur = __hip_atomic_load(&cand->rep, __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == 0ULL) {
+            cur = atomicCAS(&cand->rep, 0ULL, rep);
+            if (cur == 0ULL) {
+                __hip_atomic_store(&cand->pfx[0], pf.x,
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&cand->pfx[1], pf.y,
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&cand->ident, my_ident,
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                *claimed = 1;
+                return cand;
+            }
+        }
+        if (cur == rep) return cand;
+        const uint64_t oident = __hip_atomic_load(&cand->ident, __ATOMIC_RELAXED,
+                                                  __HIP_MEMORY_SCOPE_AGENT);
+        if (oident != 0) {
+            if (oident != my_ident) continue;
+            if (my_len <= 16) {
+                uint64_t p0 = __hip_atomic_load(&cand->pfx[0], __ATOMIC_RELAXED,
+                                                __HIP_MEMORY_SCOPE_AGENT);
+                uint64_t p1 = __hip_atomic_load(&cand->pfx[1], __ATOMIC_RELAXED,
+                                                __HIP_MEMORY_SCOPE_AGENT);
+                if (p0 == pf.x && p1 == pf.y) return cand;
+            }
+        }
+        /* unpublished identity, long key, or prefix not visible yet: decide
+         * exactly from the owner's dictionary entry */
+        const int oseg = (int)(cur >> 32) - 1;
+        const int64_t oid = (int64_t)(cur & 0xFFFFFFFFULL);
+        if (hashes[acc_base[oseg] + oid - 1] != h) continue;
+        uint32_t mlen, olen;
+        const char* mp = dict_entry(segs[key_seg_off + lo], segex[key_seg_off + lo],
+                                    g - acc_base[lo], &mlen);
+        const char* op = dict_entry(segs[key_seg_off + oseg],
+                                    segex[key_seg_off + oseg], oid - 1, &olen);
+        if (olen != mlen) continue;
+        uint32_t k = 0;
+        while (k < mlen && op[k] == mp[k]) k++;
+        if (k == mlen) return cand;
+    }
+    return nullptr;
+}
+
+/* G2: fold every dictionary entry that kept at least one row into its
+ * slot's aggregate record slot_aggs[stride * slot index] (same layout as
+ * the accumulator record; counts are full 64-bit words). An entry whose
+ * rows were all filtered out is skipped, so it creates no group. The
+ * claimer leaves the slot's own index in StrSlot.sum_bits: k_strgrp_compact
+ * copies that word into OutStrGroup.sum_bits, which is how k_strgen_gather
+ * finds each compacted group's record. */
+__global__ void __launch_bounds__(256)
+k_strgen_merge(const DevSeg* segs, const SegEx* segex, int key_seg_off, int nsegs,
+               const int64_t* acc_base, const unsigned long long* acc,
+               StrGenAggs ag, const uint64_t* hashes, const uint64_t* idents,
+               const ulonglong2* pfxs, StrSlot* slots, uint64_t nslots,
+               unsigned long long* slot_aggs, TableHdr* th)
+{
+    const int64_t total = acc_base[nsegs];
+    const int stride = 1 + 2 * ag.count;
+    __shared__ unsigned long long s_claims;
+    if (threadIdx.x == 0) s_claims = 0;
+    __syncthreads();
+    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         g < total; g += (int64_t)gridDim.x * blockDim.x) {
+        const unsigned long long* rec = acc + (uint64_t)stride * (uint64_t)g;
+        if (rec[0] == 0) continue;
+        int claimed;
+        StrSlot* slot = strgrp_find_slot(segs, segex, key_seg_off, nsegs, acc_base,
+                                         g, hashes, idents, pfxs, slots,
+                                         nslots - 1, &claimed);
+        if (!slot) { th->overflow = 1; continue; }
+        const uint64_t sidx = (uint64_t)(slot - slots);
+        if (claimed) {
+            slot->sum_bits = sidx;
+            atomicAdd(&s_claims, 1ULL);
+        }
+        unsigned long long* sa = slot_aggs + (uint64_t)stride * sidx;
+        atomicAdd(sa, rec[0]);
+        for (int a = 0; a < ag.count; a++) {
+            const unsigned long long bits = rec[1 + 2 * a];
+            const unsigned long long nn = rec[2 + 2 * a];
+            const int f = ag.func[a];
+            if (f == YT_AGG_SUM1 || nn == 0) continue;
+            unsigned long long* ap = sa + 1 + 2 * a;
+            if (f == YT_AGG_FIRST) {
+                if (atomicCAS(ap + 1, 0ULL, 1ULL) == 0ULL) ap[0] = bits;
+                continue;
+            }
+            if (f == YT_AGG_MIN || f == YT_AGG_MAX) {
+                atomicMax(ap, bits);            /* already ord_map'ped */
+            } else if (ag.is_double[a]) {
+                atomicAdd((double*)ap, __longlong_as_double(bits));
+            } else {
+                atomicAdd(ap, bits);
+            }
+            atomicAdd(ap + 1, nn);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_claims) {
+        unsigned long long t = atomicAdd(&th->ngroups, s_claims);
+        if (th->group_limit > 0 && (int64_t)(t + s_claims) > th->group_limit)
+            mark_group_limit(th);
+    }
+}
+
+/* G3: after k_strgrp_compact — fetch each compacted group's aggregate
+ * record through the slot index left in OutStrGroup.sum_bits. With
+ * pack_state (two-phase bottom query, one sum + sum(1)s) the group is also
+ * rewritten in place into the specialised path's {sum_bits, cnt|nonnull}
+ * form, which is what the k_strst_* partition kernels read. */
+__global__ void __launch_bounds__(256)
+k_strgen_gather(OutStrGroup* groups, int64_t n, const unsigned long long* slot_aggs,
+                uint64_t nslots, int agg_count, OutStrAgg* out,
+                int pack_state, int sum_slot)
+{
+    const int stride = 1 + 2 * agg_count;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t sidx = groups[i].sum_bits;
+        if (sidx >= nslots) continue;
+        const unsigned long long* sa = slot_aggs + (uint64_t)stride * sidx;
+        OutStrAgg o;
+        o.cnt = sa[0];
+        for (int a = 0; a < kMaxAggs; a++) {
+            o.agg_bits[a] = a < agg_count ? sa[1 + 2 * a] : 0;
+            o.agg_nonnull[a] = a < agg_count ? sa[2 + 2 * a] : 0;
+        }
+        out[i] = o;
+        if (pack_state) {
+            groups[i].sum_bits = sum_slot >= 0 ? o.agg_bits[sum_slot] : 0;
+            groups[i].cnt_nonnull = (o.cnt & 0xFFFFFFFFULL)
+                | ((sum_slot >= 0 ? o.agg_nonnull[sum_slot] : 0) << 32);
+        }
+    }
+}
+
+/* ------------------------------------------------------------------ */
 /* table compaction / partition / merge                                */
 
 __global__ void k_compact(TableHdr* th, const unsigned long long* slots,
@@ -3963,6 +4266,56 @@ hipError_t ytql_launch_strgrp_compact(const DevSeg* segs, const SegEx* segex,
     hipLaunchKernelGGL(k_strgrp_compact, dim3(grid), dim3(256), 0, st,
                        segs, segex, key_seg_off, slots, nslots, out, counter,
                        pool, pool_cursor, pool_cap, th);
+    return hipGetLastError();
+}
+
+hipError_t ytql_launch_strgen_accum(const DevPlan* p, const DevSeg* segs,
+                                    const SegEx* segex,
+                                    const int32_t* col_seg_off,
+                                    const int32_t* col_seg_cnt,
+                                    int key_col, int64_t row_count,
+                                    const int64_t* acc_base,
+                                    unsigned long long* acc, TableHdr* th,
+                                    unsigned* error_out, hipStream_t st)
+{
+    int64_t want = (row_count + kStrGenTile - 1) / kStrGenTile;
+    int grid = (int)(want > 4096 ? 4096 : (want > 0 ? want : 1));
+    hipLaunchKernelGGL(k_strgen_accum, dim3(grid), dim3(256), 0, st,
+                       *p, segs, segex, col_seg_off, col_seg_cnt, key_col,
+                       row_count, acc_base, acc, th, error_out);
+    return hipGetLastError();
+}
+
+hipError_t ytql_launch_strgen_merge(const DevSeg* segs, const SegEx* segex,
+                                    int key_seg_off, int nsegs,
+                                    const int64_t* acc_base,
+                                    const unsigned long long* acc,
+                                    const StrGenAggs* ag,
+                                    const uint64_t* hashes,
+                                    const uint64_t* idents, const ulonglong2* pfxs,
+                                    StrSlot* slots, uint64_t nslots,
+                                    unsigned long long* slot_aggs, TableHdr* th,
+                                    int64_t total, hipStream_t st)
+{
+    int64_t want = (total + 255) / 256;
+    int grid = (int)(want > 4096 ? 4096 : (want ? want : 1));
+    hipLaunchKernelGGL(k_strgen_merge, dim3(grid), dim3(256), 0, st,
+                       segs, segex, key_seg_off, nsegs, acc_base, acc, *ag,
+                       hashes, idents, pfxs, slots, nslots, slot_aggs, th);
+    return hipGetLastError();
+}
+
+hipError_t ytql_launch_strgen_gather(OutStrGroup* groups, int64_t n,
+                                     const unsigned long long* slot_aggs,
+                                     uint64_t nslots, int agg_count,
+                                     OutStrAgg* out, int pack_state,
+                                     int sum_slot, hipStream_t st)
+{
+    int64_t want = (n + 255) / 256;
+    int grid = (int)(want > 2048 ? 2048 : (want ? want : 1));
+    hipLaunchKernelGGL(k_strgen_gather, dim3(grid), dim3(256), 0, st,
+                       groups, n, slot_aggs, nslots, agg_count, out,
+                       pack_state, sum_slot);
     return hipGetLastError();
 }
 
