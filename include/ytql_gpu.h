@@ -108,10 +108,36 @@ enum {
     YT_EX_LIT_I64 = 1,
     YT_EX_LIT_NULL = 2,
     YT_EX_LIT_DOUBLE = 3,
+    YT_EX_LIT_STRING = 4, /* leaf: lit_len bytes at lit_str (not NUL-terminated) */
     YT_EX_ADD = 10, YT_EX_SUB = 11, YT_EX_MUL = 12, YT_EX_DIV = 13, YT_EX_MOD = 14,
     YT_EX_EQ = 20, YT_EX_NE = 21, YT_EX_LT = 22, YT_EX_LE = 23, YT_EX_GT = 24, YT_EX_GE = 25,
     YT_EX_AND = 30, YT_EX_OR = 31, YT_EX_NOT = 32,
+    /* string functions: one STRING column against one string literal */
+    YT_EX_IS_PREFIX = 40, /* is_prefix(a = literal prefix, b = column) */
+    YT_EX_IS_SUBSTR = 41, /* is_substr(a = literal pattern, b = column) */
+    YT_EX_LIKE = 42,      /* a = column LIKE b = literal pattern; lit_i64 =
+                             escape byte 0..255, or -1 for none */
 };
+
+/* String predicates (GPU entries; plan->filter only, anywhere inside its
+ * AND/OR/NOT tree). A leaf is
+ *   - EQ..GE between a plain STRING column and a YT_EX_LIT_STRING or
+ *     YT_EX_LIT_NULL, in either order, or
+ *   - IS_PREFIX / IS_SUBSTR / LIKE in exactly the argument shapes above.
+ * Semantics are byte-wise. Relational: memcmp over the shorter length, then
+ * the shorter string is less, bytes unsigned; a null text follows the
+ * non-canonical relational rule (null < any value, null == null, non-null
+ * Boolean result). The three functions give null for a null text; the empty
+ * literal is a prefix and a substring of everything. LIKE is anchored to the
+ * whole text: '%' matches any byte sequence, '_' exactly ONE BYTE (not one
+ * code point), escape + byte matches that byte literally; a pattern ending
+ * in a lone escape is YT_ERR_INVALID_PLAN. Anything else that mixes strings
+ * into an expression is refused: string column against string column, a
+ * string literal against a non-string operand or in arithmetic
+ * (YT_ERR_INVALID_PLAN), strings in key expressions, aggregate arguments,
+ * projections and HAVING, string predicates beside a join, and more than 4
+ * string predicates in one filter. The CPU oracle does not know these
+ * nodes. */
 
 typedef struct YtExpr {
     int32_t op;           /* YT_EX_* */
@@ -120,6 +146,8 @@ typedef struct YtExpr {
     double lit_dbl;       /* for YT_EX_LIT_DOUBLE */
     const struct YtExpr* a;
     const struct YtExpr* b;
+    const char* lit_str;  /* for YT_EX_LIT_STRING */
+    int64_t lit_len;
 } YtExpr;
 
 enum {
@@ -139,8 +167,9 @@ enum {
                              double(sum)/count */
     /* With one STRING group key every function above is available (1..4
      * aggregates, arguments any expression over int64/uint64/double/boolean
-     * columns), beside a WHERE clause over non-string columns. A STRING
-     * column inside a filter or an aggregate argument is refused. */
+     * columns), beside any WHERE clause the int64-key path takes, string
+     * predicates on the key column or another STRING column included. A
+     * STRING column inside an aggregate argument is refused. */
 };
 
 typedef struct YtAgg {
@@ -461,6 +490,11 @@ enum {
 };
 uint32_t yt_gpu_debug_last_scan_path(void);
 
+/* Diagnostic only: dictionary entries (runs / rows for the direct layouts)
+ * on which the calling thread's last query evaluated string predicates,
+ * summed over its predicates; 0 when it had none. */
+uint64_t yt_gpu_debug_last_strpred_entries(void);
+
 /* Two-phase (coordinated) path, mirroring the bottom/front query split
  * (engine_api/coordinator.h:26,78,89; shuffle engine_api/shuffling_reader.cpp:21-88).
  *
@@ -623,6 +657,15 @@ void yt_encoded_column_free(YtEncodedColumn* col);
  * Returns words written. */
 int64_t yt_bitpack_size_words(uint64_t max_value, int64_t n);
 int64_t yt_bitpack(const uint64_t* values, int64_t n, uint64_t max_value, uint64_t* dst);
+
+/* One string predicate on one non-null text, exposed for format tests: the
+ * host build of the matchers the GPU entry pass runs. op = YT_EX_EQ..GE
+ * (text against lit), YT_EX_IS_PREFIX / IS_SUBSTR (lit = prefix / pattern)
+ * or YT_EX_LIKE (lit = pattern; escape = byte 0..255 or -1). Returns 0 or
+ * 1, or a negative value for an unknown op or a pattern ending in a lone
+ * escape. Needs no GPU. */
+int yt_strpred_eval(int op, int escape, const char* text, int64_t text_len,
+                    const char* lit, int64_t lit_len);
 
 #ifdef __cplusplus
 } /* extern "C" */

@@ -41,9 +41,11 @@ EX_COLUMN = 0
 EX_LIT_I64 = 1
 EX_LIT_NULL = 2
 EX_LIT_DOUBLE = 3
+EX_LIT_STRING = 4
 EX_ADD, EX_SUB, EX_MUL, EX_DIV, EX_MOD = 10, 11, 12, 13, 14
 EX_EQ, EX_NE, EX_LT, EX_LE, EX_GT, EX_GE = 20, 21, 22, 23, 24, 25
 EX_AND, EX_OR, EX_NOT = 30, 31, 32
+EX_IS_PREFIX, EX_IS_SUBSTR, EX_LIKE = 40, 41, 42
 
 AGG_SUM = 0
 AGG_SUM1 = 1
@@ -98,7 +100,8 @@ class YtExpr(C.Structure):
 
 YtExpr._fields_ = [("op", C.c_int32), ("col", C.c_int32),
                    ("lit_i64", C.c_int64), ("lit_dbl", C.c_double),
-                   ("a", C.POINTER(YtExpr)), ("b", C.POINTER(YtExpr))]
+                   ("a", C.POINTER(YtExpr)), ("b", C.POINTER(YtExpr)),
+                   ("lit_str", C.c_void_p), ("lit_len", C.c_int64)]
 
 
 class YtAgg(C.Structure):
@@ -238,6 +241,9 @@ def gpu_lib():
              [C.POINTER(YtPlan), C.POINTER(YtChunk), C.POINTER(YtExecOptions),
               C.POINTER(YtRowset), C.POINTER(YtStatistics), C.c_char_p, C.c_size_t])
         _sig(lib, "yt_gpu_debug_last_scan_path", C.c_uint32, [])
+        _sig(lib, "yt_gpu_debug_last_strpred_entries", C.c_uint64, [])
+        _sig(lib, "yt_strpred_eval", C.c_int,
+             [C.c_int, C.c_int, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64])
         _sig(lib, "yt_gpu_query_partial", C.c_int,
              [C.POINTER(YtPlan), C.POINTER(YtChunk), C.POINTER(YtExecOptions),
               C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),

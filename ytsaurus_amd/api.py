@@ -11,14 +11,16 @@ from ._abi import (
     YtValue, YtSegment, YtColumn, YtChunk, YtExpr, YtAgg, YtPlan,
     YtExecOptions, YtStatistics, YtRowset, YtStateRow, YtEncodedColumn,
     VT_NULL, VT_INT64, VT_UINT64, VT_DOUBLE, VT_BOOLEAN, VT_STRING,
-    EX_COLUMN, EX_LIT_I64, EX_LIT_NULL, EX_LIT_DOUBLE,
+    EX_COLUMN, EX_LIT_I64, EX_LIT_NULL, EX_LIT_DOUBLE, EX_LIT_STRING,
+    EX_IS_PREFIX, EX_IS_SUBSTR, EX_LIKE,
     EX_ADD, EX_SUB, EX_MUL, EX_DIV, EX_MOD,
     EX_EQ, EX_NE, EX_LT, EX_LE, EX_GT, EX_GE, EX_AND, EX_OR, EX_NOT,
     AGG_SUM, AGG_SUM1, AGG_MIN, AGG_MAX, AGG_FIRST, AGG_AVG, YT_OK,
 )
 
 __all__ = [
-    "col", "lit", "null", "litf", "Plan", "Join", "agg_sum", "agg_sum1",
+    "col", "lit", "null", "litf", "lit_str", "is_prefix", "is_substr", "like",
+    "strpred_eval", "Plan", "Join", "agg_sum", "agg_sum1",
     "agg_first", "agg_avg", "agg_min", "agg_max",
     "encode_int64", "encode_double", "encode_bool", "encode_string", "encode_string_raw",
     "oracle_decode_strings", "encode_versioned_int64", "encode_versioned_double", "encode_versioned_string", "oracle_versioned_read", "gpu_versioned_read", "gpu_versioned_scan_chunk", "gpu_versioned_scan_table", "ScanChunk", "VersionedColumn",
@@ -36,9 +38,15 @@ __all__ = [
 class Expr:
     """Builds YtExpr trees; keeps ctypes objects alive via _keep."""
 
-    def __init__(self, op, col=-1, lit_i64=0, lit_dbl=0.0, a=None, b=None):
+    def __init__(self, op, col=-1, lit_i64=0, lit_dbl=0.0, a=None, b=None,
+                 lit_str=None):
         self.c = YtExpr(op=op, col=col, lit_i64=lit_i64, lit_dbl=lit_dbl)
         self._keep = []
+        if lit_str is not None:
+            buf = C.create_string_buffer(lit_str, max(len(lit_str), 1))
+            self.c.lit_str = C.addressof(buf)
+            self.c.lit_len = len(lit_str)
+            self._keep.append(buf)
         if a is not None:
             self.c.a = C.pointer(a.c)
             self._keep.append(a)
@@ -77,6 +85,8 @@ def _coerce(x):
         return litf(x)
     if x is None:
         return null()
+    if isinstance(x, (bytes, bytearray, str)):
+        return lit_str(x)
     raise TypeError(x)
 
 
@@ -94,6 +104,67 @@ def litf(v):
 
 def null():
     return Expr(EX_LIT_NULL)
+
+
+def _bytes(b):
+    return b.encode() if isinstance(b, str) else bytes(b)
+
+
+def lit_str(b):
+    """string literal: bytes, or str (UTF-8 encoded)"""
+    return Expr(EX_LIT_STRING, lit_str=_bytes(b))
+
+
+def is_prefix(prefix, expr):
+    """is_prefix(prefix, text) — the reference's argument order; null text
+    gives null"""
+    return Expr(EX_IS_PREFIX, a=_coerce(prefix), b=_coerce(expr))
+
+
+def is_substr(pattern, expr):
+    """is_substr(pattern, text); null text gives null"""
+    return Expr(EX_IS_SUBSTR, a=_coerce(pattern), b=_coerce(expr))
+
+
+def like(expr, pattern, escape=None):
+    """text LIKE pattern [ESCAPE escape], byte-wise and anchored: % matches
+    any byte sequence, _ exactly one BYTE, escape + byte that byte literally.
+    escape: one byte (bytes/str of length 1) or None."""
+    esc = -1
+    if escape is not None:
+        eb = _bytes(escape)
+        if len(eb) != 1:
+            raise ValueError("like: escape must be exactly one byte")
+        esc = eb[0]
+    return Expr(EX_LIKE, lit_i64=esc, a=_coerce(expr), b=_coerce(pattern))
+
+
+def strpred_eval(op, text, literal, escape=None):
+    """TEST ONLY: one string predicate on one non-null text through the host
+    build of the GPU matchers (yt_strpred_eval). Returns 0/1, negative on
+    error."""
+    esc = -1 if escape is None else _bytes(escape)[0]
+    t, l = _bytes(text), _bytes(literal)
+    return _abi.gpu_lib().yt_strpred_eval(op, esc, t, len(t), l, len(l))
+
+
+def _has_string_nodes(e):
+    """does a YtExpr tree (ctypes) hold a node the oracle does not know?"""
+    if e is None:
+        return False
+    if e.c.op in (EX_LIT_STRING, EX_IS_PREFIX, EX_IS_SUBSTR, EX_LIKE):
+        return True
+    return any(_has_string_nodes(k) for k in e._keep if isinstance(k, Expr))
+
+
+def _oracle_refuse_strings(plan):
+    """The oracle's eval_expr would dereference the NULL children of an
+    unknown leaf: never hand it a plan with string literals / functions."""
+    exprs = [plan.filter, plan.having] + list(plan.keys) + list(plan.projects)
+    exprs += [arg for _, arg in plan.aggs]
+    if any(_has_string_nodes(e) for e in exprs):
+        raise NotImplementedError(
+            "the CPU oracle has no string literals or string predicates")
 
 
 def agg_sum(e):
@@ -778,6 +849,7 @@ def _attach_join_dev(plan, join_foreign):
 
 def oracle_execute(plan, chunk, nthreads=1, expect_error=False):
     """TEST/BASELINE ONLY — runs the CPU oracle restatement."""
+    _oracle_refuse_strings(plan)
     _j = _attach_join(plan, lambda c: c.c_host())
     ch = chunk.c_host()
     rs = _mk_rowset(max(chunk.row_count + 16, 1 << 16), pool_bytes=32 << 20)
@@ -792,6 +864,7 @@ def oracle_execute(plan, chunk, nthreads=1, expect_error=False):
 
 
 def oracle_partial(plan, chunk, nparts, nthreads=1):
+    _oracle_refuse_strings(plan)
     _j = _attach_join(plan, lambda c: c.c_host())
     ch = chunk.c_host()
     cap = chunk.row_count + 16
@@ -807,6 +880,7 @@ def oracle_partial(plan, chunk, nparts, nthreads=1):
 def oracle_partial_mk(plan, chunk, nparts, key_ranges, nthreads=1):
     """multi-key bottom query: key_ranges = (zzmin list, zzmax list) reduced
     across ranks (yt_gpu_key_ranges / oracle equivalents)."""
+    _oracle_refuse_strings(plan)
     _j = _attach_join(plan, lambda c: c.c_host())
     ch = chunk.c_host()
     cap = chunk.row_count + 16
@@ -823,6 +897,7 @@ def oracle_partial_mk(plan, chunk, nparts, key_ranges, nthreads=1):
 
 
 def oracle_merge_mk(plan, states_list, key_ranges, col_types=None):
+    _oracle_refuse_strings(plan)
     total = sum(n for _, n in states_list)
     arr = (YtStateRow * max(total, 1))()
     at = 0
@@ -898,6 +973,7 @@ def gpu_merge_mk(plan, states_dev_ptr, n_states, key_ranges, col_types=None,
 def oracle_merge(plan, states_list):
     """states_list: list of (YtStateRow array-like, count) or a flat numpy
     structured buffer."""
+    _oracle_refuse_strings(plan)
     total = sum(n for _, n in states_list)
     flat = (YtStateRow * max(total, 1))()
     at = 0
@@ -996,7 +1072,7 @@ def gpu_available():
 
 def gpu_execute(plan, device_chunk, max_groups_hint=0, group_row_limit=0,
                 stream=0, out_capacity=None, rowset=None, raw_rowset=False,
-                join_foreign=None):
+                join_foreign=None, input_row_limit=0):
     """device_chunk: YtChunk with device pointers (Chunk.c_device).
     Pass a preallocated `rowset` (from make_rowset) to avoid per-call
     allocation; raw_rowset=True skips the Python row conversion.
@@ -1004,7 +1080,8 @@ def gpu_execute(plan, device_chunk, max_groups_hint=0, group_row_limit=0,
     when the plan has a join)."""
     _j = _attach_join_dev(plan, join_foreign)
     opts = YtExecOptions(max_groups_hint=max_groups_hint,
-                         group_row_limit=group_row_limit, stream=stream)
+                         group_row_limit=group_row_limit, stream=stream,
+                         input_row_limit=input_row_limit)
     if rowset is not None:
         rs = rowset
     else:
@@ -1043,6 +1120,7 @@ def oracle_partial_str(plan, chunk, nparts, nthreads=1):
     """string-keyed bottom query: returns (states ctypes array, counts list,
     pool bytes, pool_bytes-per-partition list). Each partition's states are
     contiguous; key_bits reference that partition's pool slice."""
+    _oracle_refuse_strings(plan)
     ch = chunk.c_host()
     cap = chunk.row_count + 16
     pool_cap = 64 + 32 * chunk.row_count
@@ -1063,6 +1141,7 @@ def oracle_partial_str(plan, chunk, nparts, nthreads=1):
 def oracle_merge_str(plan, segments, out_capacity=None, pool_capacity=None):
     """segments: list of (states ctypes array/list, count, pool bytes obj,
     pool_byte_count) received by this partition, in a fixed order."""
+    _oracle_refuse_strings(plan)
     nseg = len(segments)
     total = sum(s[1] for s in segments)
     allst = (YtStateRow * max(total, 1))()

@@ -45,7 +45,19 @@ enum POp : int32_t {
     P_ADD = 10, P_SUB = 11, P_MUL = 12, P_DIV = 13, P_MOD = 14,
     P_EQ = 20, P_NE = 21, P_LT = 22, P_LE = 23, P_GT = 24, P_GE = 25,
     P_AND = 30, P_OR = 31, P_NOT = 32,
+    /* one whole string-predicate leaf (a STRING column against a literal):
+     * col = the column; bits = predicate index (low 8 bits) | kSpNullRes /
+     * kSpNullIsNull = the answer for a null text | kSpConst / kSpConstRes =
+     * the answer for every non-null text is a constant (comparison with the
+     * null literal), no bitmap. Otherwise the answer for entry id is bit
+     * sp_base[pred][seg]*64 + id-1 of sp_bits[pred] (k_strpred_entries). */
+    P_STR_PRED = 50,
 };
+
+constexpr uint64_t kSpNullRes = 1ULL << 8;
+constexpr uint64_t kSpNullIsNull = 1ULL << 9;
+constexpr uint64_t kSpConst = 1ULL << 10;
+constexpr uint64_t kSpConstRes = 1ULL << 11;
 
 struct PInst {
     int32_t op;
@@ -56,6 +68,7 @@ struct PInst {
 constexpr int kMaxProg = 48;
 constexpr int kMaxCols = 8;
 constexpr int kMaxAggs = 4;
+constexpr int kMaxStrPreds = 4;    /* string predicates with a bitmap per filter */
 
 /* One compiled plan for the device: programs are concatenated postfix
  * streams with (offset,len) per role. */
@@ -90,6 +103,12 @@ struct DevPlan {
     int32_t proj_off[kMaxProj], proj_len[kMaxProj];
     PInst prog[kMaxProg];
     int32_t prog_len;
+    /* string predicates (P_STR_PRED): per predicate the entry-answer bitmap
+     * and, per kept segment of its column, the bitmap's first 64-bit word.
+     * Device pointers, filled by the host after the segment parse. */
+    int32_t sp_count;
+    const uint64_t* sp_bits[kMaxStrPreds];
+    const int64_t* sp_base[kMaxStrPreds];
 };
 
 /* Equi-join device context (one join item, UNIQUE foreign keys — see

@@ -21,6 +21,7 @@
 #include <atomic>
 
 #include "common.h"
+#include "strpred.h"
 #include "../../include/ytql_gpu.h"
 
 using namespace ytql;
@@ -126,6 +127,10 @@ hipError_t ytql_launch_strgrp_compact(const DevSeg*, const SegEx*, int,
                                       const StrSlot*, uint64_t, OutStrGroup*,
                                       unsigned long long*, char*, unsigned long long*,
                                       uint64_t, TableHdr*, hipStream_t);
+hipError_t ytql_launch_strpred_entries(const DevSeg*, const SegEx*, int, int,
+                                       const int64_t*, int64_t, int, int,
+                                       const char*, int64_t, uint64_t*,
+                                       hipStream_t);
 hipError_t ytql_launch_strgen_accum(const DevPlan*, const DevSeg*, const SegEx*,
                                     const int32_t*, const int32_t*, int, int64_t,
                                     const int64_t*, unsigned long long*,
@@ -377,14 +382,246 @@ static bool expr_reads_string(const YtExpr* e, const uint8_t* col_types, int nco
     if (e->op == YT_EX_COLUMN)
         return e->col >= 0 && e->col < ncols && col_types[e->col] == YT_VT_STRING;
     if (e->op == YT_EX_LIT_I64 || e->op == YT_EX_LIT_NULL ||
-        e->op == YT_EX_LIT_DOUBLE)
+        e->op == YT_EX_LIT_DOUBLE || e->op == YT_EX_LIT_STRING)
         return false;
     return expr_reads_string(e->a, col_types, ncols) ||
            (e->op != YT_EX_NOT && expr_reads_string(e->b, col_types, ncols));
 }
 
+/* does the expression hold a string literal or a string function? Only a
+ * filter's string-predicate leaves may (compile_filter). */
+static bool expr_has_strlit(const YtExpr* e)
+{
+    if (!e) return false;
+    if (e->op == YT_EX_LIT_STRING ||
+        (e->op >= YT_EX_IS_PREFIX && e->op <= YT_EX_LIKE))
+        return true;
+    if (e->op == YT_EX_COLUMN || e->op == YT_EX_LIT_I64 ||
+        e->op == YT_EX_LIT_NULL || e->op == YT_EX_LIT_DOUBLE)
+        return false;
+    return expr_has_strlit(e->a) ||
+           (e->op != YT_EX_NOT && expr_has_strlit(e->b));
+}
+
+/* ------------------------------------------------------------------ */
+/* string predicates: a STRING column against a literal, in the filter.
+ * A leaf depends on the column's ENTRY only (dictionary entry, run or row,
+ * kernels.hip str_key_id), so it is evaluated once per entry into a bitmap
+ * (k_strpred_entries) and each row reads one bit (P_STR_PRED). */
+
+struct StrPredDesc {
+    int op;                /* YT_EX_EQ..GE (column on the left), IS_PREFIX,
+                              IS_SUBSTR or LIKE */
+    int escape;            /* LIKE: 0..255, or -1 */
+    int col;
+    const char* lit;       /* the plan's bytes; alive for the whole call */
+    int64_t lit_len;
+};
+
+struct StrPreds {
+    int count = 0;                  /* leaves that need a bitmap */
+    bool any = false;               /* any leaf, bitmap-less ones included */
+    StrPredDesc d[kMaxStrPreds];
+    std::vector<void*> bufs;        /* pooled device buffers of this run */
+    std::vector<int64_t> h_base[kMaxStrPreds];   /* upload sources */
+
+    ~StrPreds()
+    {
+        for (void* b : bufs) g_pool.put(b);
+    }
+};
+
+static thread_local uint64_t t_last_strpred_entries = 0;
+
+extern "C" uint64_t yt_gpu_debug_last_strpred_entries(void)
+{
+    return t_last_strpred_entries;
+}
+
+extern "C" int yt_strpred_eval(int op, int escape, const char* text,
+                               int64_t text_len, const char* lit,
+                               int64_t lit_len)
+{
+    if (text_len < 0 || lit_len < 0 || (text_len && !text) || (lit_len && !lit))
+        return -1;
+    if (op == YT_EX_LIKE) {
+        if (escape < -1 || escape > 255) return -1;
+        if (strpred_like_bad_pattern(lit, lit_len, escape)) return -2;
+    }
+    return strpred_eval(op, escape, text, text_len, lit, lit_len);
+}
+
+static int emit_inst(DevPlan* p, int op, int col, uint64_t bits,
+                     char* errbuf, size_t errlen)
+{
+    if (p->prog_len >= kMaxProg) { set_err(errbuf, errlen, "expression too long"); return YT_ERR_INVALID_PLAN; }
+    PInst& in = p->prog[p->prog_len++];
+    in.op = op;
+    in.col = col;
+    in.bits = bits;
+    return YT_OK;
+}
+
+static bool is_string_col(const YtExpr* e, const DevPlan* p)
+{
+    return e && e->op == YT_EX_COLUMN && e->col >= 0 && e->col < p->ncols &&
+           p->col_types[e->col] == YT_VT_STRING;
+}
+
+/* recognise one string-predicate leaf and compile it into one P_STR_PRED;
+ * *matched = 0 when e is no such leaf (and nothing was emitted) */
+static int compile_str_leaf(const YtExpr* e, DevPlan* p, StrPreds* sp,
+                            int* matched, char* errbuf, size_t errlen)
+{
+    *matched = 0;
+    StrPredDesc d;
+    memset(&d, 0, sizeof(d));
+    d.escape = -1;
+    const YtExpr* lit = nullptr;
+    if (e->op >= YT_EX_EQ && e->op <= YT_EX_GE) {
+        int op = e->op;
+        const YtExpr* colx = nullptr;
+        if (is_string_col(e->a, p)) {
+            colx = e->a; lit = e->b;
+        } else if (is_string_col(e->b, p)) {
+            /* literal on the left: flip the operator */
+            colx = e->b; lit = e->a;
+            switch (op) {
+            case YT_EX_LT: op = YT_EX_GT; break;
+            case YT_EX_LE: op = YT_EX_GE; break;
+            case YT_EX_GT: op = YT_EX_LT; break;
+            case YT_EX_GE: op = YT_EX_LE; break;
+            default: break;
+            }
+        } else {
+            return YT_OK;
+        }
+        if (!lit || (lit->op != YT_EX_LIT_STRING && lit->op != YT_EX_LIT_NULL))
+            return YT_OK;
+        d.op = op;
+        d.col = colx->col;
+        if (lit->op == YT_EX_LIT_NULL) {
+            /* null < any value, null == null: a constant per null and per
+             * non-null text — no bitmap */
+            const int lt_null = 0, eq_null = 1;      /* null text vs null */
+            const int lt_val = 0, eq_val = 0;        /* value vs null */
+            auto res = [&](int lt, int eq) -> bool {
+                switch (op) {
+                case YT_EX_EQ: return eq;
+                case YT_EX_NE: return !eq;
+                case YT_EX_LT: return lt;
+                case YT_EX_LE: return lt || eq;
+                case YT_EX_GT: return !(lt || eq);
+                default: return !lt;
+                }
+            };
+            uint64_t bits = kSpConst;
+            if (res(lt_null, eq_null)) bits |= kSpNullRes;
+            if (res(lt_val, eq_val)) bits |= kSpConstRes;
+            sp->any = true;
+            *matched = 1;
+            return emit_inst(p, P_STR_PRED, d.col, bits, errbuf, errlen);
+        }
+    } else if (e->op == YT_EX_IS_PREFIX || e->op == YT_EX_IS_SUBSTR) {
+        if (!e->a || e->a->op != YT_EX_LIT_STRING || !is_string_col(e->b, p)) {
+            set_err(errbuf, errlen,
+                    "type mismatch: is_prefix / is_substr take (string "
+                    "literal, plain string column)");
+            return YT_ERR_INVALID_PLAN;
+        }
+        d.op = e->op;
+        d.col = e->b->col;
+        lit = e->a;
+    } else if (e->op == YT_EX_LIKE) {
+        if (!e->b || e->b->op != YT_EX_LIT_STRING || !is_string_col(e->a, p)) {
+            set_err(errbuf, errlen,
+                    "type mismatch: LIKE takes (plain string column, string "
+                    "literal)");
+            return YT_ERR_INVALID_PLAN;
+        }
+        if (e->lit_i64 < -1 || e->lit_i64 > 255) {
+            set_err(errbuf, errlen, "LIKE: escape must be one byte or -1");
+            return YT_ERR_INVALID_PLAN;
+        }
+        d.op = e->op;
+        d.col = e->a->col;
+        d.escape = (int)e->lit_i64;
+        lit = e->b;
+    } else {
+        return YT_OK;
+    }
+    if (lit->lit_len < 0 || (lit->lit_len > 0 && !lit->lit_str)) {
+        set_err(errbuf, errlen, "string literal without bytes");
+        return YT_ERR_INVALID_PLAN;
+    }
+    d.lit = lit->lit_str;
+    d.lit_len = lit->lit_len;
+    if (d.op == YT_EX_LIKE &&
+        strpred_like_bad_pattern(d.lit, d.lit_len, d.escape)) {
+        set_err(errbuf, errlen, "LIKE: pattern ends in a lone escape");
+        return YT_ERR_INVALID_PLAN;
+    }
+    if (sp->count >= kMaxStrPreds) {
+        set_err(errbuf, errlen,
+                "more than 4 string predicates in one filter: not this round");
+        return YT_ERR_UNSUPPORTED;
+    }
+    /* a null text: the relational ops answer by the null rule (null < any
+     * value), the functions answer null */
+    uint64_t bits = (uint64_t)sp->count;
+    if (d.op >= YT_EX_EQ && d.op <= YT_EX_GE) {
+        if (d.op == YT_EX_NE || d.op == YT_EX_LT || d.op == YT_EX_LE)
+            bits |= kSpNullRes;
+    } else {
+        bits |= kSpNullIsNull;
+    }
+    sp->d[sp->count++] = d;
+    sp->any = true;
+    *matched = 1;
+    return emit_inst(p, P_STR_PRED, d.col, bits, errbuf, errlen);
+}
+
+static int compile_expr(const YtExpr* e, DevPlan* p, int* len, char* errbuf, size_t errlen);
+
+/* the filter: AND/OR/NOT over string-predicate leaves and ordinary
+ * subexpressions; sp == nullptr refuses every string predicate */
+static int compile_filter(const YtExpr* e, DevPlan* p, StrPreds* sp,
+                          char* errbuf, size_t errlen)
+{
+    if (!e) { set_err(errbuf, errlen, "null expr"); return YT_ERR_INVALID_PLAN; }
+    if (e->op == YT_EX_AND || e->op == YT_EX_OR || e->op == YT_EX_NOT) {
+        int rc = compile_filter(e->a, p, sp, errbuf, errlen);
+        if (rc) return rc;
+        if (e->op != YT_EX_NOT) {
+            rc = compile_filter(e->b, p, sp, errbuf, errlen);
+            if (rc) return rc;
+        }
+        return emit_inst(p, e->op, e->col, 0, errbuf, errlen);
+    }
+    if (sp) {
+        int matched = 0;
+        int rc = compile_str_leaf(e, p, sp, &matched, errbuf, errlen);
+        if (rc || matched) return rc;
+    }
+    if (expr_has_strlit(e)) {
+        set_err(errbuf, errlen,
+                "type mismatch: a string literal compares with a plain "
+                "string column only");
+        return YT_ERR_INVALID_PLAN;
+    }
+    if (expr_reads_string(e, p->col_types, p->ncols)) {
+        set_err(errbuf, errlen,
+                "string column inside a filter or key expression: "
+                "unsupported on the GPU (string predicates take one plain "
+                "string column and one literal)");
+        return YT_ERR_UNSUPPORTED;
+    }
+    int len = 0;
+    return compile_expr(e, p, &len, errbuf, errlen);
+}
+
 static int build_devplan(const YtPlan* plan, const YtChunk* chunk, DevPlan* p,
-                         char* errbuf, size_t errlen)
+                         StrPreds* sp, char* errbuf, size_t errlen)
 {
     memset(p, 0, sizeof(*p));
     p->ncols = chunk->column_count;
@@ -463,19 +700,25 @@ static int build_devplan(const YtPlan* plan, const YtChunk* chunk, DevPlan* p,
     }
 
     int rc;
-    if (expr_reads_string(plan->filter, p->col_types, p->ncols) ||
-        (plan->key_count == 1 && plan->keys[0]->op != YT_EX_COLUMN &&
-         expr_reads_string(plan->keys[0], p->col_types, p->ncols))) {
+    if (plan->key_count == 1 && plan->keys[0]->op != YT_EX_COLUMN &&
+        (expr_reads_string(plan->keys[0], p->col_types, p->ncols) ||
+         expr_has_strlit(plan->keys[0]))) {
         set_err(errbuf, errlen,
                 "string column inside a filter or key expression: "
-                "unsupported on the GPU (no string predicates)");
+                "unsupported on the GPU (string predicates belong to the "
+                "filter)");
         return YT_ERR_UNSUPPORTED;
     }
     if (plan->filter) {
         p->filter_off = p->prog_len;
-        rc = compile_expr(plan->filter, p, &p->filter_len, errbuf, errlen);
+        rc = compile_filter(plan->filter, p, sp, errbuf, errlen);
         if (rc) return rc;
         p->filter_len = p->prog_len - p->filter_off;
+        if (sp && sp->any && plan->join) {
+            set_err(errbuf, errlen,
+                    "string predicate beside a join: not this round");
+            return YT_ERR_UNSUPPORTED;
+        }
     }
     if (plan->key_count == 1) {
         p->key_off = p->prog_len;
@@ -512,7 +755,8 @@ static int build_devplan(const YtPlan* plan, const YtChunk* chunk, DevPlan* p,
             }
         }
         if (plan->aggs[a]->func != YT_AGG_SUM1 &&
-            expr_reads_string(plan->aggs[a]->arg, p->col_types, p->ncols)) {
+            (expr_reads_string(plan->aggs[a]->arg, p->col_types, p->ncols) ||
+             expr_has_strlit(plan->aggs[a]->arg))) {
             set_err(errbuf, errlen,
                     "string column inside an aggregate argument: "
                     "unsupported on the GPU");
@@ -528,6 +772,12 @@ static int build_devplan(const YtPlan* plan, const YtChunk* chunk, DevPlan* p,
     if (plan->agg_count == 0) {
         p->proj_count = plan->project_count;
         for (int pj = 0; pj < plan->project_count; pj++) {
+            if (expr_has_strlit(plan->projects[pj])) {
+                set_err(errbuf, errlen,
+                        "string literal or predicate inside a projection: "
+                        "unsupported on the GPU");
+                return YT_ERR_UNSUPPORTED;
+            }
             p->proj_off[pj] = p->prog_len;
             rc = compile_expr(plan->projects[pj], p, &p->proj_len[pj], errbuf, errlen);
             if (rc) return rc;
@@ -940,6 +1190,86 @@ static int setup_chunk(const YtChunk* chunk, DeviceRun* R, unsigned* maxw_out,
     HIP_CHECK(hipStreamSynchronize(R->stream));
     return YT_OK;
 fail:
+    return rc;
+}
+
+/* String predicates, after setup_chunk: for every predicate read back its
+ * column's parsed segments (the KEPT ones — input_row_limit truncates the
+ * list), lay the per-segment bitmaps out on 64-bit word boundaries, run the
+ * entry pass on the run's stream and hand bitmap + bases to the plan. The
+ * buffers live in sp until the run ends. */
+static int setup_string_preds(StrPreds* sp, DeviceRun* R, DevPlan* dp,
+                              char* errbuf, size_t errlen)
+{
+    int rc = YT_OK;
+    uint64_t entries = 0;
+    const bool timing = getenv("YTQL_TIMING") != nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    t_last_strpred_entries = 0;
+    dp->sp_count = sp->count;
+    if (sp->count == 0 || R->nsegs == 0) return YT_OK;
+    if (timing) {
+        HIP_CHECK(hipEventCreate(&e0));
+        HIP_CHECK(hipEventCreate(&e1));
+        HIP_CHECK(hipEventRecord(e0, R->stream));
+    }
+    for (int i = 0; i < sp->count; i++) {
+        const StrPredDesc& d = sp->d[i];
+        const int off = R->h_off[d.col], cnt = R->h_cnt[d.col];
+        if (cnt == 0) continue;
+        std::vector<SegEx> ex(cnt);
+        HIP_CHECK(hipMemcpy(ex.data(), R->d_segex + off, sizeof(SegEx) * cnt,
+                            hipMemcpyDeviceToHost));
+        std::vector<int64_t>& base = sp->h_base[i];
+        base.resize(cnt + 1);
+        int64_t words = 0;
+        for (int sg = 0; sg < cnt; sg++) {
+            if (!(ex[sg].flags & (8 | 32 | 64))) {
+                set_err(errbuf, errlen,
+                        "string predicate: unknown string segment layout");
+                rc = YT_ERR_UNSUPPORTED;
+                goto fail;
+            }
+            base[sg] = words;
+            words += ((int64_t)ex[sg].dict_size + 63) / 64;
+            entries += ex[sg].dict_size;
+        }
+        base[cnt] = words;
+        int64_t* d_base = nullptr;
+        uint64_t* d_bits = nullptr;
+        char* d_lit = nullptr;
+        HIP_CHECK(pool_alloc(&d_base, sizeof(int64_t) * (cnt + 1)));
+        sp->bufs.push_back(d_base);
+        HIP_CHECK(pool_alloc(&d_bits, sizeof(uint64_t) * (words ? words : 1)));
+        sp->bufs.push_back(d_bits);
+        HIP_CHECK(pool_alloc(&d_lit, (size_t)(d.lit_len ? d.lit_len : 1)));
+        sp->bufs.push_back(d_lit);
+        HIP_CHECK(hipMemcpyAsync(d_base, base.data(), sizeof(int64_t) * (cnt + 1),
+                                 hipMemcpyHostToDevice, R->stream));
+        if (d.lit_len)
+            HIP_CHECK(hipMemcpyAsync(d_lit, d.lit, (size_t)d.lit_len,
+                                     hipMemcpyHostToDevice, R->stream));
+        if (words)
+            HIP_CHECK(ytql_launch_strpred_entries(R->d_segs, R->d_segex, off, cnt,
+                                                  d_base, words, d.op, d.escape,
+                                                  d_lit, d.lit_len, d_bits,
+                                                  R->stream));
+        dp->sp_bits[i] = d_bits;
+        dp->sp_base[i] = d_base;
+    }
+    t_last_strpred_entries = entries;
+    if (timing) {
+        float ms = 0;
+        HIP_CHECK(hipEventRecord(e1, R->stream));
+        HIP_CHECK(hipEventSynchronize(e1));
+        HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+        fprintf(stderr, "[ytql timing] string predicates: %d, %llu entries, "
+                        "entry pass %.3fms\n",
+                sp->count, (unsigned long long)entries, ms);
+    }
+fail:
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
     return rc;
 }
 
@@ -2077,6 +2407,10 @@ static int finish_output(const YtPlan* plan, YtRowset* out,
     const int64_t had_group_rows = out->row_count;
     if (plan->with_totals && !after) fold_totals_rows(plan, out, tot);
     if (plan->having) {
+        if (expr_has_strlit(plan->having)) {
+            set_err(errbuf, errlen, "HAVING over string values: not this round");
+            return YT_ERR_UNSUPPORTED;
+        }
         int ncols = out->column_count;
         uint64_t mask = 0;
         hexpr_cols(plan->having, &mask);
@@ -2145,6 +2479,7 @@ static int finish_output(const YtPlan* plan, YtRowset* out,
  * filter/projection the generic path supports works here. */
 static int run_scan_topk(const YtPlan* plan, const YtChunk* chunk,
                          const YtExecOptions* options, const DevPlan* dp,
+                         StrPreds* sp,
                          const JoinDev* jd, const JoinDev* jd2,
                          YtRowset* output, YtStatistics* stats, double tw0,
                          char* errbuf, size_t errlen)
@@ -2160,12 +2495,16 @@ static int run_scan_topk(const YtPlan* plan, const YtChunk* chunk,
     }
 
     DeviceRun R2;
+    DevPlan dpl = *dp;      /* + this run's string-predicate bitmaps */
     R2.stream = (hipStream_t)(uintptr_t)options->stream;
     unsigned mw = 0;
     int in_clamped = 0;
     rc = setup_chunk(chunk, &R2, &mw, options->input_row_limit, &in_clamped,
                      errbuf, errlen);
     if (rc) return rc;
+    rc = setup_string_preds(sp, &R2, &dpl, errbuf, errlen);
+    if (rc) return rc;
+    dp = &dpl;
     if (stats) stats->decode_time_ms = now_ms() - tw0;   /* setup phase */
     int64_t n = chunk->row_count;
     if (options->input_row_limit > 0 && options->input_row_limit < n)
@@ -2521,18 +2860,23 @@ fail:
  * and a pass mask; the host compacts in row order. */
 static int run_scan_project(const YtPlan* plan, const YtChunk* chunk,
                             const YtExecOptions* options, const DevPlan* dp,
+                            StrPreds* sp,
                             const JoinDev* jd, const JoinDev* jd2,
                             YtRowset* output, YtStatistics* stats, double tw0,
                             char* errbuf, size_t errlen)
 {
     int rc = YT_OK;
     DeviceRun R2;
+    DevPlan dpl = *dp;      /* + this run's string-predicate bitmaps */
     R2.stream = (hipStream_t)(uintptr_t)options->stream;
     unsigned mw = 0;
     int in_clamped = 0;
     rc = setup_chunk(chunk, &R2, &mw, options->input_row_limit, &in_clamped,
                      errbuf, errlen);
     if (rc) return rc;
+    rc = setup_string_preds(sp, &R2, &dpl, errbuf, errlen);
+    if (rc) return rc;
+    dp = &dpl;
     (void)in_clamped;
     int64_t n = chunk->row_count;
     if (options->input_row_limit > 0 && options->input_row_limit < n)
@@ -2776,12 +3120,13 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
         }
     }
     DevPlan dp;
+    StrPreds SP;
     uint8_t sum_type[kMaxAggs];
     if (general) {
         /* the interpreter's plan: compiles filter + aggregate arguments and
          * carries its refusals (string columns in expressions, avg + WITH
          * TOTALS, more than kMaxAggs aggregates, ...) */
-        rc = build_devplan(plan, chunk, &dp, errbuf, errlen);
+        rc = build_devplan(plan, chunk, &dp, &SP, errbuf, errlen);
         if (rc) return rc;
         for (int a = 0; a < plan->agg_count; a++) {
             sum_type[a] = (plan->aggs[a]->func != YT_AGG_SUM1)
@@ -2825,6 +3170,10 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
     rc = setup_table(&R, plan->agg_count, options->max_groups_hint,
                      options->group_row_limit, errbuf, errlen);
     if (rc) return rc;
+    if (general) {
+        rc = setup_string_preds(&SP, &R, &dp, errbuf, errlen);
+        if (rc) return rc;
+    }
 
     /* read back the parsed key-column segments: dictionary sizes + layout */
     int knseg = R.h_cnt[key_col];
@@ -3784,6 +4133,11 @@ extern "C" int yt_gpu_query_execute(
         return YT_ERR_INVALID_PLAN;
     }
     output->totals_row = 0;
+    t_last_strpred_entries = 0;
+    if (plan->having && expr_has_strlit(plan->having)) {
+        set_err(errbuf, errlen, "HAVING over string values: not this round");
+        return YT_ERR_UNSUPPORTED;
+    }
     if (plan->with_totals || plan->having) {
         if (plan->key_count == 0) {
             set_err(errbuf, errlen, "WITH TOTALS / HAVING requires GROUP BY");
@@ -3824,7 +4178,8 @@ extern "C" int yt_gpu_query_execute(
     }
 
     DevPlan dp;
-    rc = build_devplan(plan, chunk, &dp, errbuf, errlen);
+    StrPreds SP;
+    rc = build_devplan(plan, chunk, &dp, &SP, errbuf, errlen);
     if (rc) return rc;
 
     JoinRun JR[2];
@@ -3848,15 +4203,19 @@ extern "C" int yt_gpu_query_execute(
     if (plan->agg_count == 0 && plan->key_count == 0) {
         if (plan->order_count > 0) {
             /* scan + ORDER BY ... LIMIT: k-selection, no full materialization */
-            return run_scan_topk(plan, chunk, options, &dp, jd, jd2, output,
-                                 stats, tw0, errbuf, errlen);
+            return run_scan_topk(plan, chunk, options, &dp, &SP, jd, jd2,
+                                 output, stats, tw0, errbuf, errlen);
         }
-        return run_scan_project(plan, chunk, options, &dp, jd, jd2, output,
-                                stats, tw0, errbuf, errlen);
+        return run_scan_project(plan, chunk, options, &dp, &SP, jd, jd2,
+                                output, stats, tw0, errbuf, errlen);
     }
 
     FastShape fs;
     analyze_fast(plan, chunk, &fs);
+    /* a string predicate runs in the interpreter only. analyze_fast refuses
+     * any chunk that holds a non-int64 column, so this never fires; it is
+     * stated so that it does not depend on that */
+    if (SP.any) fs.valid = 0;
 
     DeviceRun R;
     R.stream = (hipStream_t)(uintptr_t)options->stream;
@@ -3886,6 +4245,8 @@ extern "C" int yt_gpu_query_execute(
     rc = setup_table(&R, plan->agg_count,
                      options->max_groups_hint,
                      options->group_row_limit, errbuf, errlen);
+    if (rc) return rc;
+    rc = setup_string_preds(&SP, &R, &dp, errbuf, errlen);
     if (rc) return rc;
 
     const bool timing = getenv("YTQL_TIMING") != nullptr;   /* phase breakdown to stderr */
@@ -4021,11 +4382,14 @@ static int query_partial_impl(
     if (stats) memset(stats, 0, sizeof(*stats));
 
     double tw0 = now_ms();
+    t_last_strpred_entries = 0;
     DevPlan dp;
-    rc = build_devplan(plan, chunk, &dp, errbuf, errlen);
+    StrPreds SP;
+    rc = build_devplan(plan, chunk, &dp, &SP, errbuf, errlen);
     if (rc) return rc;
     FastShape fs;
     analyze_fast(plan, chunk, &fs);
+    if (SP.any) fs.valid = 0;     /* interpreter only, as in yt_gpu_query_execute */
 
     DeviceRun R;
     R.stream = (hipStream_t)(uintptr_t)options->stream;
@@ -4055,6 +4419,8 @@ static int query_partial_impl(
     }
     rc = setup_table(&R, plan->agg_count, options->max_groups_hint,
                      options->group_row_limit, errbuf, errlen);
+    if (rc) return rc;
+    rc = setup_string_preds(&SP, &R, &dp, errbuf, errlen);
     if (rc) return rc;
     double tq0 = now_ms();
     JoinRun JRp[2];
@@ -4220,6 +4586,7 @@ extern "C" int yt_gpu_query_partial_str(
     memset(&defopt, 0, sizeof(defopt));
     if (!options) options = &defopt;
     if (stats) memset(stats, 0, sizeof(*stats));
+    t_last_strpred_entries = 0;
     StrPartialOut po;
     po.partition_count = partition_count;
     po.states_device = (YtStateRow*)states_device;

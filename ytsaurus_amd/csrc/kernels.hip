@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "common.h"
+#include "strpred.h"
 #include "../../include/ytql_gpu.h"
 
 namespace ytql {
@@ -171,9 +172,10 @@ __global__ void k_parse_segments(const DevSeg* segs, int nsegs, SegEx* out,
     SegEx e = {};
     const uint64_t* b = s.blob;
     if (s.type == YT_SEG_DOUBLE) {
-        /* [u64 count][doubles][null bitmap] */
+        /* [u64 count][doubles][null bitmap]. The blob's own count places the
+         * bitmap: input_row_limit may have clamped s.row_count below it. */
         e.off_doubles_bytes = 8;
-        e.off_bitmap_bytes = 8 + 8 * (int64_t)s.row_count;
+        e.off_bitmap_bytes = 8 + 8 * (int64_t)b[0];
         e.w_values = 64;
     } else if (s.is_signed == 2) {
         /* STRING column — string_column_writer.cpp dump layouts.
@@ -228,7 +230,9 @@ __global__ void k_parse_segments(const DevSeg* segs, int nsegs, SegEx* out,
             e.dict_size = (uint32_t)n0;      /* = row_count */
             e.off_values_words = 1;
             e.off_bitmap_bytes = words0 * 8;
-            int64_t bm = (((int64_t)s.row_count + 7) / 8 + 7) & ~(int64_t)7;
+            /* one bitmap bit per stored row (n0), not per kept row:
+             * input_row_limit may have clamped s.row_count */
+            int64_t bm = (((int64_t)n0 + 7) / 8 + 7) & ~(int64_t)7;
             e.off_doubles_bytes = words0 * 8 + bm;
             e.flags |= 32;  /* direct-dense string segment */
             break;
@@ -263,7 +267,7 @@ __global__ void k_parse_segments(const DevSeg* segs, int nsegs, SegEx* out,
     } else if (s.type == YT_SEG_BOOLEAN) {
         /* [u64 count][value bitmap][null bitmap], both 8-aligned */
         e.off_doubles_bytes = 8;     /* value bitmap */
-        e.off_bitmap_bytes = 8 + (((int64_t)s.row_count + 7) / 8 + 7) / 8 * 8;
+        e.off_bitmap_bytes = 8 + (((int64_t)b[0] + 7) / 8 + 7) / 8 * 8;
         e.w_values = 1;
     } else {
         uint64_t h0 = b[0];
@@ -646,6 +650,48 @@ __device__ __forceinline__ bool join_row_ok(const DevPlan& p, ColCtx& c)
     return true;
 }
 
+__device__ __forceinline__ uint64_t str_key_id(const DevSeg& sk, const SegEx& ek,
+                                               int64_t j);
+
+/* P_STR_PRED: the row's answer to one string predicate (common.h). The
+ * predicate was evaluated once per ENTRY of the column's segments by
+ * k_strpred_entries; a row looks its entry id up and reads one bit. Kept
+ * out of line: inlined into eval_prog it cost k_topk_materialize 9 VGPRs and
+ * one wave of occupancy; out of line every interpreter kernel keeps the
+ * register count it had before this instruction existed. */
+__device__ __noinline__ DVal str_pred_row(const DevPlan& p, const ColCtx& c, const PInst& in)
+{
+    const int off = c.col_seg_off[in.col];
+    int lo;
+    if (p.col_uniform_shift[in.col]) {
+        lo = (int)(c.row >> p.col_uniform_shift[in.col]);
+    } else {
+        int hi = c.col_seg_cnt[in.col];
+        lo = 0;
+        while (lo + 1 < hi) {
+            int mid = (lo + hi) / 2;
+            if (c.segs[off + mid].start_row <= c.row) lo = mid;
+            else hi = mid;
+        }
+    }
+    const DevSeg& s = c.segs[off + lo];
+    const uint64_t id = str_key_id(s, c.segex[off + lo], c.row - s.start_row);
+    DVal v;
+    v.type = YT_VT_BOOLEAN;
+    v.null_ = 0;
+    if (id == 0) {
+        if (in.bits & kSpNullIsNull) { v.type = YT_VT_NULL; v.null_ = 1; v.bits = 0; }
+        else v.bits = (in.bits & kSpNullRes) != 0;
+    } else if (in.bits & kSpConst) {
+        v.bits = (in.bits & kSpConstRes) != 0;
+    } else {
+        const int pi = (int)(in.bits & 0xFF);
+        const uint64_t bit = (uint64_t)p.sp_base[pi][lo] * 64 + (id - 1);
+        v.bits = (p.sp_bits[pi][bit >> 6] >> (bit & 63)) & 1;
+    }
+    return v;
+}
+
 __device__ DVal eval_prog(const DevPlan& p, ColCtx& c, int off, int len)
 {
     DVal stk[12];
@@ -677,6 +723,9 @@ __device__ DVal eval_prog(const DevPlan& p, ColCtx& c, int off, int len)
             stk[sp++] = a;
             break;
         }
+        case P_STR_PRED:
+            stk[sp++] = str_pred_row(p, c, in);
+            break;
         default: {
             DVal b = stk[--sp];
             DVal a = stk[--sp];
@@ -3123,6 +3172,46 @@ __device__ __forceinline__ uint64_t str_key_id(const DevSeg& sk, const SegEx& ek
     return bp_get(sk.blob + ek.off_ids_words, ek.w_ids, lo);
 }
 
+/* String predicate entry pass (common.h P_STR_PRED): evaluate ONE predicate
+ * (op, escape, literal) on every entry of every segment of its column and
+ * leave one answer bit per entry — bit id-1 of the segment's bitmap, which
+ * starts at word pred_base[seg]. One wave64 owns one 64-bit word: a lane per
+ * entry, __ballot assembles the word, lane 0 stores it. Every word of
+ * [0, pred_base[nsegs]) is written exactly once, so the buffer needs no
+ * memset and no atomics; lanes past dict_size contribute 0. Null entries
+ * (direct layouts) get an arbitrary bit: null rows never look it up. */
+__global__ void __launch_bounds__(256)
+k_strpred_entries(const DevSeg* segs, const SegEx* segex, int seg_off, int nsegs,
+                  const int64_t* pred_base, int op, int escape,
+                  const char* lit, int64_t lit_len, uint64_t* bits)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t nwords = pred_base[nsegs];
+    const int64_t wstride = (int64_t)gridDim.x * 4;
+    for (int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); w < nwords;
+         w += wstride) {
+        /* the last segment whose first word <= w: segments without entries
+         * own no word and are stepped over */
+        int lo = 0, hi = nsegs;
+        while (lo + 1 < hi) {
+            int mid = (lo + hi) / 2;
+            if (pred_base[mid] <= w) lo = mid;
+            else hi = mid;
+        }
+        const DevSeg& s = segs[seg_off + lo];
+        const SegEx& e = segex[seg_off + lo];
+        const int64_t j = (w - pred_base[lo]) * 64 + lane;
+        int res = 0;
+        if (j < (int64_t)e.dict_size) {
+            uint32_t len;
+            const char* t = dict_entry(s, e, j, &len);
+            res = strpred_eval(op, escape, t, (int64_t)len, lit, lit_len) > 0;
+        }
+        const unsigned long long word = __ballot(res);
+        if (lane == 0) bits[w] = word;
+    }
+}
+
 /* G1: per row — filter, aggregate arguments (eval_prog), then
  * agg_update_slot into the row's record
  *   acc[stride * (acc_base[seg] + id-1)] = { rows, {bits, nonnull} per agg }
@@ -4266,6 +4355,21 @@ hipError_t ytql_launch_strgrp_compact(const DevSeg* segs, const SegEx* segex,
     hipLaunchKernelGGL(k_strgrp_compact, dim3(grid), dim3(256), 0, st,
                        segs, segex, key_seg_off, slots, nslots, out, counter,
                        pool, pool_cursor, pool_cap, th);
+    return hipGetLastError();
+}
+
+hipError_t ytql_launch_strpred_entries(const DevSeg* segs, const SegEx* segex,
+                                       int seg_off, int nsegs,
+                                       const int64_t* pred_base,
+                                       int64_t nwords, int op, int escape,
+                                       const char* lit, int64_t lit_len,
+                                       uint64_t* bits, hipStream_t st)
+{
+    int64_t want = (nwords + 3) / 4;      /* one wave64 per word */
+    int grid = (int)(want > 4096 ? 4096 : (want > 0 ? want : 1));
+    hipLaunchKernelGGL(k_strpred_entries, dim3(grid), dim3(256), 0, st,
+                       segs, segex, seg_off, nsegs, pred_base, op, escape,
+                       lit, lit_len, bits);
     return hipGetLastError();
 }
 
