@@ -134,10 +134,28 @@ enum {
  * in a lone escape is YT_ERR_INVALID_PLAN. Anything else that mixes strings
  * into an expression is refused: string column against string column, a
  * string literal against a non-string operand or in arithmetic
- * (YT_ERR_INVALID_PLAN), strings in key expressions, aggregate arguments,
- * projections and HAVING, string predicates beside a join, and more than 4
- * string predicates in one filter. The CPU oracle does not know these
- * nodes. */
+ * (YT_ERR_INVALID_PLAN), strings in key expressions, aggregate arguments
+ * and HAVING, string literals and predicates inside a projection, string
+ * predicates beside a join, and more than 4 string predicates in one filter.
+ * The CPU oracle does not know these nodes. */
+
+/* STRING projections (GPU entries; plain scans: agg_count == 0 and
+ * key_count == 0). A projection that is exactly YT_EX_COLUMN over a STRING
+ * column of the primary chunk returns that column: YtValue{type
+ * YT_VT_STRING, length, data.str} with the bytes appended to
+ * YtRowset.string_pool (string_pool_used grows by exactly the sum of the
+ * emitted lengths; a pool that cannot take them is YT_ERR_CAPACITY; a null
+ * or zero-capacity pool is fine when that sum is 0). A null value stays
+ * YT_VT_NULL; an empty non-null string is YT_VT_STRING with length 0. Rows
+ * come in input row order, or in ORDER BY order when the plan sorts on its
+ * other (non-string) projections. Any projection count, the same column more
+ * than once, any filter the scan takes (string predicates included) and
+ * input_row_limit / output_row_limit work as for numeric projections.
+ * Refused with YT_ERR_UNSUPPORTED: a STRING column inside a projection
+ * EXPRESSION (col + 1, col == col, ...), a STRING projection beside a join,
+ * a foreign STRING value column, and a STRING projection used as an ORDER BY
+ * column of a plain scan. The CPU oracle's scan mode has no string
+ * projections. */
 
 typedef struct YtExpr {
     int32_t op;           /* YT_EX_* */
@@ -469,7 +487,7 @@ int yt_gpu_query_execute(
     YtStatistics* stats,
     char* errbuf, size_t errlen);
 
-/* Diagnostic only: YT_SCAN_PATH_* bits of the calling thread's last grouped scan. */
+/* Diagnostic only: YT_SCAN_PATH_* bits of the calling thread's last query. */
 enum {
     YT_SCAN_PATH_PARTITIONED = 1 << 0,  /* partitioned group-by attempted */
     YT_SCAN_PATH_DIRECT      = 1 << 1,  /* direct-span phase B chosen */
@@ -487,6 +505,11 @@ enum {
                                            DirectRle key segment */
     YT_SCAN_PATH_STR_GENERAL = 1 << 10, /* general kernels: filter, any aggregate
                                            mix, ragged segments, DirectRle keys */
+    /* plain scans (no aggregate, no key) report this bit or 0 */
+    YT_SCAN_PATH_PROJ_COMPACT = 1 << 11, /* scan + project with a STRING
+                                            projection: device compaction and
+                                            byte gather; 0 after any other plain
+                                            scan, with or without ORDER BY */
 };
 uint32_t yt_gpu_debug_last_scan_path(void);
 

@@ -66,6 +66,7 @@ SCAN_PATH_FAST = 1 << 7
 SCAN_PATH_GENERIC = 1 << 8
 SCAN_PATH_STR_DENSE = 1 << 9
 SCAN_PATH_STR_GENERAL = 1 << 10
+SCAN_PATH_PROJ_COMPACT = 1 << 11
 
 
 class YtValueData(C.Union):

@@ -771,7 +771,10 @@ def rows_from_rowset(rs):
             elif v.type == VT_BOOLEAN:
                 row.append(bool(v.data.bits))
             elif v.type == VT_STRING:
-                row.append(C.string_at(v.data.str, v.length))
+                # the address, not the c_char_p view: that one stops at the
+                # first 0x00 byte
+                row.append(C.string_at(v.data.u64, v.length)
+                           if v.length else b"")
             else:
                 row.append(("?", v.type, v.data.bits))
         out.append(tuple(row))
@@ -1072,21 +1075,25 @@ def gpu_available():
 
 def gpu_execute(plan, device_chunk, max_groups_hint=0, group_row_limit=0,
                 stream=0, out_capacity=None, rowset=None, raw_rowset=False,
-                join_foreign=None, input_row_limit=0):
+                join_foreign=None, input_row_limit=0, output_row_limit=0,
+                pool_bytes=None):
     """device_chunk: YtChunk with device pointers (Chunk.c_device).
     Pass a preallocated `rowset` (from make_rowset) to avoid per-call
     allocation; raw_rowset=True skips the Python row conversion.
     join_foreign: device YtChunk for plan.join's foreign rowset (required
-    when the plan has a join)."""
+    when the plan has a join). pool_bytes sizes the string pool of the
+    rowset made here (default 32 MiB; 0 = no pool)."""
     _j = _attach_join_dev(plan, join_foreign)
     opts = YtExecOptions(max_groups_hint=max_groups_hint,
                          group_row_limit=group_row_limit, stream=stream,
-                         input_row_limit=input_row_limit)
+                         input_row_limit=input_row_limit,
+                         output_row_limit=output_row_limit)
     if rowset is not None:
         rs = rowset
     else:
         cap = out_capacity or max(int(max_groups_hint) * 2 + 1024, 1 << 16)
-        rs = _mk_rowset(cap, pool_bytes=32 << 20)
+        rs = _mk_rowset(cap, pool_bytes=32 << 20 if pool_bytes is None
+                        else pool_bytes)
     st = YtStatistics()
     err = C.create_string_buffer(512)
     rc = _abi.gpu_lib().yt_gpu_query_execute(

@@ -52,6 +52,11 @@ enum POp : int32_t {
      * null literal), no bitmap. Otherwise the answer for entry id is bit
      * sp_base[pred][seg]*64 + id-1 of sp_bits[pred] (k_strpred_entries). */
     P_STR_PRED = 50,
+    /* a whole projection that is one STRING column of the primary chunk
+     * (plain scans only): col = the column. Yields type YT_VT_STRING, or null,
+     * and bits = (global DevSeg index << 32) | (entry id - 1): the entry that
+     * dict_entry() resolves to the value's bytes (StrGatherRec.ref). */
+    P_STR_REF = 51,
 };
 
 constexpr uint64_t kSpNullRes = 1ULL << 8;
@@ -161,10 +166,32 @@ struct VSegDev {
     const char* val_data;
 };
 
-/* device output value for the scan+project path (16 B) */
+/* device output value for the scan+project path (16 B). A YT_VT_STRING
+ * value holds its entry reference in bits (P_STR_REF) as the interpreter
+ * leaves it; after the compaction / length pass pad_ = its length in bytes,
+ * and in the rows sent to the host bits = its byte offset in the pool. */
 struct DevOutVal {
     uint64_t bits;
     uint32_t type;     /* YT_VT_*; YT_VT_NULL for null */
+    uint32_t pad_;
+};
+
+/* scan+project with STRING projections (kernels.hip k_proj_*, k_str_*).
+ * The window is compacted on the device in tiles of kProjTile rows; a tile's
+ * total is {passing rows, bytes of their non-null string values}. */
+constexpr int kProjTile = 2048;
+struct ProjTot {
+    unsigned long long rows;
+    unsigned long long bytes;
+};
+
+/* one string value to copy: entry `ref` (P_STR_REF bits) -> pool[dst, dst+len).
+ * ref == kStrRefNull stands for a null value: len 0, nothing copied. */
+constexpr uint64_t kStrRefNull = ~0ULL;
+struct StrGatherRec {
+    uint64_t ref;
+    uint64_t dst;
+    uint32_t len;
     uint32_t pad_;
 };
 

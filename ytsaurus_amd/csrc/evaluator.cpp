@@ -95,6 +95,17 @@ hipError_t ytql_launch_scan_project(const DevPlan*, const DevSeg*, const SegEx*,
                                     const int32_t*, const int32_t*, int64_t,
                                     int64_t, const JoinDev*, const JoinDev*,
                                     DevOutVal*, uint8_t*, unsigned*, hipStream_t);
+hipError_t ytql_launch_proj_offsets(const DevSeg*, const SegEx*, DevOutVal*,
+                                    const uint8_t*, int64_t, int, unsigned,
+                                    ProjTot*, ProjTot*, hipStream_t);
+hipError_t ytql_launch_proj_scatter(const DevOutVal*, const uint8_t*, int64_t,
+                                    int, unsigned, int, const ProjTot*,
+                                    DevOutVal*, StrGatherRec*, hipStream_t);
+hipError_t ytql_launch_str_reclen(const DevSeg*, const SegEx*, StrGatherRec*,
+                                  int64_t, hipStream_t);
+hipError_t ytql_launch_str_gather(const DevSeg*, const SegEx*,
+                                  const StrGatherRec*, int64_t, char*, uint64_t,
+                                  hipStream_t);
 hipError_t ytql_launch_scan_generic(const DevPlan*, const DevSeg*, const SegEx*,
                                     const int32_t*, const int32_t*, int64_t,
                                     const JoinDev*, const JoinDev*,
@@ -779,6 +790,38 @@ static int build_devplan(const YtPlan* plan, const YtChunk* chunk, DevPlan* p,
                 return YT_ERR_UNSUPPORTED;
             }
             p->proj_off[pj] = p->prog_len;
+            int sc;
+            if (expr_is_col(plan->projects[pj], &sc) && sc >= 0 &&
+                sc < p->ncols && p->col_types[sc] == YT_VT_STRING) {
+                /* a bare STRING column: one P_STR_REF, plain scans only */
+                const char* why = nullptr;
+                if (sc >= chunk->column_count)
+                    why = "foreign string column in a projection: not this round";
+                else if (plan->join)
+                    why = "string projection beside a join: not this round";
+                else if (plan->key_count > 0)
+                    why = "string projection outside a plain scan: unsupported "
+                          "on the GPU";
+                for (int i = 0; !why && i < plan->order_count; i++)
+                    if (plan->order_cols && plan->order_cols[i] == pj)
+                        why = "ORDER BY on a string column in a plain scan: "
+                              "not this round";
+                if (why) {
+                    set_err(errbuf, errlen, why);
+                    return YT_ERR_UNSUPPORTED;
+                }
+                rc = emit_inst(p, P_STR_REF, sc, 0, errbuf, errlen);
+                if (rc) return rc;
+                p->proj_len[pj] = 1;
+                continue;
+            }
+            if (expr_reads_string(plan->projects[pj], p->col_types, p->ncols)) {
+                set_err(errbuf, errlen,
+                        "string column inside a projection expression: "
+                        "unsupported on the GPU (a projection may be one plain "
+                        "string column)");
+                return YT_ERR_UNSUPPORTED;
+            }
             rc = compile_expr(plan->projects[pj], p, &p->proj_len[pj], errbuf, errlen);
             if (rc) return rc;
             p->proj_len[pj] = p->prog_len - p->proj_off[pj];
@@ -1081,8 +1124,10 @@ struct DeviceRun {
     }
 };
 
-/* diagnostic: which scan path the last grouped scan on this thread took
- * (YT_SCAN_PATH_* bits); written by run_partitioned / run_scan only */
+/* diagnostic: which scan path the last query on this thread took
+ * (YT_SCAN_PATH_* bits); written by run_partitioned / run_scan /
+ * run_string_group, and by the plain-scan dispatch (0, or
+ * YT_SCAN_PATH_PROJ_COMPACT from run_scan_project) */
 static thread_local uint32_t t_last_scan_path = 0;
 
 extern "C" uint32_t yt_gpu_debug_last_scan_path(void)
@@ -2471,6 +2516,10 @@ static int finish_output(const YtPlan* plan, YtRowset* out,
     return YT_OK;
 }
 
+static unsigned string_proj_mask(const DevPlan* dp);
+static void emit_proj_value(YtValue* dst, int pj, const DevOutVal& v,
+                            char* pool_base);
+
 /* scan + ORDER BY ... LIMIT without materializing the scan: histogram
  * k-selection on an order-isomorphic u64 mapping of the first order key
  * (digits of 11 bits, host-driven refinement), then exact candidate gather
@@ -2819,6 +2868,95 @@ static int run_scan_topk(const YtPlan* plan, const YtChunk* chunk,
         int64_t e = b + plan->order_limit;
         if (e > M) e = M;
         int out_limited = 0;
+        char* pool_base = nullptr;
+        if (const unsigned str_mask = string_proj_mask(dp)) {
+            /* only the emitted slice needs bytes: its string values become
+             * gather records (row order of the slice), the device fills in
+             * the lengths, the host lays them out, k_str_gather copies */
+            int64_t ne = e - b;
+            if (options->output_row_limit > 0 && ne > options->output_row_limit)
+                ne = options->output_row_limit;    /* the loop below flags it */
+            if (ne > output->capacity_rows) {
+                put_all();
+                return YT_ERR_CAPACITY;
+            }
+            std::vector<StrGatherRec> recs;
+            std::vector<DevOutVal*> owner;
+            for (int64_t i = b; i < b + ne; i++)
+                for (int pj = 0; pj < np; pj++) {
+                    DevOutVal* v = h_vals + idx[i] * np + pj;
+                    if (!((str_mask >> pj) & 1) || v->type != YT_VT_STRING)
+                        continue;
+                    StrGatherRec g;
+                    g.ref = v->bits;
+                    g.dst = 0;
+                    g.len = 0;
+                    g.pad_ = 0;
+                    recs.push_back(g);
+                    owner.push_back(v);
+                }
+            if (!recs.empty()) {
+                const int64_t nr = (int64_t)recs.size();
+                StrGatherRec* d_recs = nullptr;
+                char* d_spool = nullptr;
+                rc = YT_OK;
+                uint64_t bytes = 0;
+                hipError_t he = pool_alloc(&d_recs, sizeof(StrGatherRec) * nr);
+                if (he == hipSuccess)
+                    he = hipMemcpy(d_recs, recs.data(), sizeof(StrGatherRec) * nr,
+                                   hipMemcpyHostToDevice);
+                if (he == hipSuccess)
+                    he = ytql_launch_str_reclen(R2.d_segs, R2.d_segex, d_recs, nr,
+                                                R2.stream);
+                if (he == hipSuccess) he = hipStreamSynchronize(R2.stream);
+                if (he == hipSuccess)
+                    he = hipMemcpy(recs.data(), d_recs, sizeof(StrGatherRec) * nr,
+                                   hipMemcpyDeviceToHost);
+                if (he == hipSuccess) {
+                    for (int64_t i = 0; i < nr; i++) {
+                        recs[i].dst = bytes;
+                        owner[i]->bits = bytes;      /* offset in this slice */
+                        owner[i]->pad_ = recs[i].len;
+                        bytes += recs[i].len;
+                    }
+                    if (bytes > 0 &&
+                        (!output->string_pool ||
+                         (uint64_t)output->string_pool_used + bytes >
+                             (uint64_t)output->string_pool_capacity)) {
+                        set_err(errbuf, errlen, "string pool too small");
+                        rc = YT_ERR_CAPACITY;
+                    }
+                }
+                if (he == hipSuccess && rc == YT_OK && bytes) {
+                    pool_base = output->string_pool + output->string_pool_used;
+                    he = pool_alloc(&d_spool, (size_t)bytes);
+                    if (he == hipSuccess)
+                        he = hipMemcpy(d_recs, recs.data(),
+                                       sizeof(StrGatherRec) * nr,
+                                       hipMemcpyHostToDevice);
+                    if (he == hipSuccess)
+                        he = ytql_launch_str_gather(R2.d_segs, R2.d_segex, d_recs,
+                                                    nr, d_spool, bytes, R2.stream);
+                    if (he == hipSuccess) he = hipStreamSynchronize(R2.stream);
+                    if (he == hipSuccess)
+                        he = hipMemcpy(pool_base, d_spool, (size_t)bytes,
+                                       hipMemcpyDeviceToHost);
+                    launches += 2;
+                }
+                g_pool.put(d_recs);
+                g_pool.put(d_spool);
+                if (he != hipSuccess) {
+                    if (errbuf) snprintf(errbuf, errlen, "HIP error %s (string gather)",
+                                         hipGetErrorString(he));
+                    rc = YT_ERR_HIP;
+                }
+                if (rc != YT_OK) {
+                    put_all();
+                    return rc;
+                }
+                output->string_pool_used += (int64_t)bytes;
+            }
+        }
         for (int64_t i = b; i < e; i++) {
             if (options->output_row_limit > 0 &&
                 output->row_count >= options->output_row_limit) {
@@ -2831,13 +2969,8 @@ static int run_scan_topk(const YtPlan* plan, const YtChunk* chunk,
             }
             const DevOutVal* src = h_vals + idx[i] * np;
             YtValue* dst = output->values + output->row_count * np;
-            for (int pj = 0; pj < np; pj++) {
-                dst[pj].id = (uint16_t)pj;
-                dst[pj].type = (uint8_t)src[pj].type;
-                dst[pj].flags = 0;
-                dst[pj].length = 0;
-                dst[pj].data.bits = src[pj].bits;
-            }
+            for (int pj = 0; pj < np; pj++)
+                emit_proj_value(dst + pj, pj, src[pj], pool_base);
             output->row_count++;
         }
         if (stats) {
@@ -2855,9 +2988,216 @@ fail:
     return rc;
 }
 
+/* bit pj set = projection pj is one P_STR_REF (a plain STRING column) */
+static unsigned string_proj_mask(const DevPlan* dp)
+{
+    unsigned m = 0;
+    for (int pj = 0; pj < dp->proj_count; pj++)
+        if (dp->proj_len[pj] == 1 && dp->prog[dp->proj_off[pj]].op == P_STR_REF)
+            m |= 1u << pj;
+    return m;
+}
+
+/* one emitted value of a scan with string projections: v is the device
+ * value, for a string with bits = byte offset inside this call's slice of
+ * the pool (which starts at pool_base) and pad_ = length */
+static void emit_proj_value(YtValue* dst, int pj, const DevOutVal& v,
+                            char* pool_base)
+{
+    dst->id = (uint16_t)pj;
+    dst->type = (uint8_t)v.type;
+    dst->flags = 0;
+    dst->length = 0;
+    dst->data.bits = v.bits;
+    if (v.type == YT_VT_STRING) {
+        dst->length = v.pad_;
+        dst->data.bits = 0;
+        dst->data.str = pool_base ? pool_base + v.bits : nullptr;
+    }
+}
+
+/* scan + filter + project with at least one STRING projection (DESIGN.md
+ * §12): per window k_scan_project, then a stable device compaction — row and
+ * byte offsets by reduce-then-scan, scatter of the survivors, byte gather
+ * into a window pool — so that only surviving rows and their bytes cross to
+ * the host. R is the set-up chunk, dp carries the string-predicate bitmaps. */
+static int scan_project_compact(const YtPlan* plan, const YtExecOptions* options,
+                                const DevPlan* dp, DeviceRun* R, int64_t n,
+                                unsigned str_mask,
+                                const JoinDev* jd, const JoinDev* jd2,
+                                YtRowset* output, YtStatistics* stats, double tw0,
+                                char* errbuf, size_t errlen)
+{
+    int rc = YT_OK;
+    const int np = plan->project_count;
+    int nstr = 0;
+    for (int pj = 0; pj < np; pj++) nstr += (str_mask >> pj) & 1;
+    const bool timing = getenv("YTQL_TIMING") != nullptr;
+    int64_t kWin = (int64_t)1 << 24;
+    if (const char* wv = getenv("YTQL_PROJ_WINDOW")) {    /* tests: small windows */
+        long long w = atoll(wv);
+        if (w < 64) w = 64;
+        if (w < kWin) kWin = w;
+    }
+    const int64_t win = n < kWin ? n : kWin;
+    const int64_t max_tiles = (win + kProjTile - 1) / kProjTile;
+    DevOutVal* d_out = nullptr;
+    uint8_t* d_pass = nullptr;
+    ProjTot* d_tiles = nullptr;      /* [max_tiles] + the window totals */
+    DevOutVal* d_cout = nullptr;
+    StrGatherRec* d_recs = nullptr;
+    char* d_pool = nullptr;
+    DevOutVal* h_out = nullptr;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    float t_scan = 0, t_off = 0, t_scat = 0, t_gath = 0;
+    double t_host = 0;
+    int windows = 0;
+    auto put_win = [&]() {
+        g_pool.put(d_cout); g_pool.put(d_recs); g_pool.put(d_pool);
+        g_pool.put(h_out);
+        d_cout = nullptr; d_recs = nullptr; d_pool = nullptr; h_out = nullptr;
+    };
+    HIP_CHECK(pool_alloc(&d_out, sizeof(DevOutVal) * win * np));
+    HIP_CHECK(pool_alloc(&d_pass, (size_t)win));
+    HIP_CHECK(pool_alloc(&d_tiles, sizeof(ProjTot) * (max_tiles + 1)));
+    for (int i = 0; i < 5; i++) HIP_CHECK(hipEventCreate(&ev[i]));
+    HIP_CHECK(hipMemsetAsync(R->d_err, 0, sizeof(unsigned), R->stream));
+    for (int64_t w0 = 0; w0 < n; w0 += win) {
+        const int64_t wlen = (w0 + win <= n) ? win : (n - w0);
+        const int ntiles = (int)((wlen + kProjTile - 1) / kProjTile);
+        ProjTot* d_totals = d_tiles + ntiles;
+        windows++;
+        HIP_CHECK(hipEventRecord(ev[0], R->stream));
+        HIP_CHECK(ytql_launch_scan_project(dp, R->d_segs, R->d_segex, R->d_off,
+                                           R->d_cnt, w0, wlen, jd, jd2, d_out,
+                                           d_pass, R->d_err, R->stream));
+        HIP_CHECK(hipEventRecord(ev[1], R->stream));
+        HIP_CHECK(ytql_launch_proj_offsets(R->d_segs, R->d_segex, d_out, d_pass,
+                                           wlen, np, str_mask, d_tiles, d_totals,
+                                           R->stream));
+        HIP_CHECK(hipEventRecord(ev[2], R->stream));
+        ProjTot tot;
+        unsigned kerr = 0;
+        HIP_CHECK(hipMemcpyAsync(&tot, d_totals, sizeof(tot),
+                                 hipMemcpyDeviceToHost, R->stream));
+        HIP_CHECK(hipMemcpyAsync(&kerr, R->d_err, sizeof(unsigned),
+                                 hipMemcpyDeviceToHost, R->stream));
+        HIP_CHECK(hipStreamSynchronize(R->stream));
+        if (kerr) {
+            set_err(errbuf, errlen, kerr == YT_ERR_DIV_ZERO ? "Division by zero" : "expression error");
+            rc = (int)kerr;
+            goto fail;
+        }
+        const int64_t wrows = (int64_t)tot.rows;
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        t_scan += ms;
+        HIP_CHECK(hipEventElapsedTime(&ms, ev[1], ev[2]));
+        t_off += ms;
+        if (wrows == 0) continue;
+
+        /* limits, in the order of the uncompacted path: output_row_limit
+         * stops the emit, then the rowset capacity, then the pool */
+        int64_t take = wrows;
+        bool limited = false;
+        if (options->output_row_limit > 0 &&
+            output->row_count + take > options->output_row_limit) {
+            take = options->output_row_limit - output->row_count;
+            limited = true;
+        }
+        if (output->row_count + take > output->capacity_rows) {
+            set_err(errbuf, errlen, "rowset too small");
+            rc = YT_ERR_CAPACITY;
+            goto fail;
+        }
+        if (take > 0) {
+            HIP_CHECK(pool_alloc(&d_cout, sizeof(DevOutVal) * wrows * np));
+            HIP_CHECK(pool_alloc(&d_recs, sizeof(StrGatherRec) * wrows * nstr));
+            HIP_CHECK(pool_alloc(&d_pool, (size_t)(tot.bytes ? tot.bytes : 1)));
+            HIP_CHECK(pool_alloc_host(&h_out, sizeof(DevOutVal) * take * np));
+            HIP_CHECK(hipEventRecord(ev[2], R->stream));
+            HIP_CHECK(ytql_launch_proj_scatter(d_out, d_pass, wlen, np, str_mask,
+                                               nstr, d_tiles, d_cout, d_recs,
+                                               R->stream));
+            HIP_CHECK(hipEventRecord(ev[3], R->stream));
+            /* records are in row order: the first take * nstr of them are
+             * the emitted rows', and their bytes a prefix of the pool */
+            if (tot.bytes)
+                HIP_CHECK(ytql_launch_str_gather(R->d_segs, R->d_segex, d_recs,
+                                                 take * nstr, d_pool, tot.bytes,
+                                                 R->stream));
+            HIP_CHECK(hipEventRecord(ev[4], R->stream));
+            HIP_CHECK(hipMemcpyAsync(h_out, d_cout, sizeof(DevOutVal) * take * np,
+                                     hipMemcpyDeviceToHost, R->stream));
+            HIP_CHECK(hipStreamSynchronize(R->stream));
+            HIP_CHECK(hipEventElapsedTime(&ms, ev[2], ev[3]));
+            t_scat += ms;
+            HIP_CHECK(hipEventElapsedTime(&ms, ev[3], ev[4]));
+            t_gath += ms;
+            const double th0 = now_ms();
+            uint64_t bytes = tot.bytes;
+            if (take < wrows) {
+                bytes = 0;
+                for (int64_t i = 0; i < take * np; i++)
+                    if (h_out[i].type == YT_VT_STRING) bytes += h_out[i].pad_;
+            }
+            if (bytes > 0 &&
+                (!output->string_pool ||
+                 (uint64_t)output->string_pool_used + bytes >
+                     (uint64_t)output->string_pool_capacity)) {
+                set_err(errbuf, errlen, "string pool too small");
+                rc = YT_ERR_CAPACITY;
+                goto fail;
+            }
+            char* pool_base = output->string_pool
+                ? output->string_pool + output->string_pool_used : nullptr;
+            if (bytes)
+                HIP_CHECK(hipMemcpy(pool_base, d_pool, (size_t)bytes,
+                                    hipMemcpyDeviceToHost));
+            YtValue* dst = output->values + output->row_count * np;
+            for (int64_t i = 0; i < take; i++)
+                for (int pj = 0; pj < np; pj++)
+                    emit_proj_value(dst + i * np + pj, pj, h_out[i * np + pj],
+                                    pool_base);
+            output->row_count += take;
+            output->string_pool_used += (int64_t)bytes;
+            t_host += now_ms() - th0;
+            put_win();
+        }
+        if (limited) {
+            if (stats) stats->incomplete_output = 1;
+            break;
+        }
+        if (options->output_row_limit > 0 &&
+            output->row_count >= options->output_row_limit)
+            break;
+    }
+    if (stats) {
+        stats->rows_read = n;
+        stats->rows_written = output->row_count;
+        stats->kernel_scan_ms += t_scan + t_off + t_scat + t_gath;
+        stats->kernel_scan_launches += 1;
+        stats->execute_time_ms = now_ms() - tw0;
+    }
+    if (timing)
+        fprintf(stderr, "[ytql timing] scan+project compact: %d window(s), "
+                        "%lld rows out, %lld pool bytes: scan %.3fms offsets "
+                        "%.3fms scatter %.3fms gather %.3fms D2H+emit %.3fms\n",
+                windows, (long long)output->row_count,
+                (long long)output->string_pool_used, t_scan, t_off, t_scat,
+                t_gath, t_host);
+fail:
+    put_win();
+    g_pool.put(d_out); g_pool.put(d_pass); g_pool.put(d_tiles);
+    for (int i = 0; i < 5; i++)
+        if (ev[i]) (void)hipEventDestroy(ev[i]);
+    return rc;
+}
+
 /* scan + filter + project: order-preserving (MakeCodegenProjectOp +
  * WriteOpHelper, registry.cpp:1999-2047). The device writes per-row values
- * and a pass mask; the host compacts in row order. */
+ * and a pass mask; the host compacts in row order. Plans with a STRING
+ * projection take scan_project_compact instead. */
 static int run_scan_project(const YtPlan* plan, const YtChunk* chunk,
                             const YtExecOptions* options, const DevPlan* dp,
                             StrPreds* sp,
@@ -2883,6 +3223,12 @@ static int run_scan_project(const YtPlan* plan, const YtChunk* chunk,
         n = options->input_row_limit;
     output->row_count = 0;
     output->column_count = plan->project_count;
+    if (const unsigned str_mask = string_proj_mask(dp)) {
+        t_last_scan_path = YT_SCAN_PATH_PROJ_COMPACT;
+        if (n == 0 || R2.nsegs == 0) return YT_OK;
+        return scan_project_compact(plan, options, dp, &R2, n, str_mask, jd, jd2,
+                                    output, stats, tw0, errbuf, errlen);
+    }
     if (n == 0 || R2.nsegs == 0) return YT_OK;
     {
         /* stream the scan through bounded windows: the per-row
@@ -4201,6 +4547,8 @@ extern "C" int yt_gpu_query_execute(
     }
 
     if (plan->agg_count == 0 && plan->key_count == 0) {
+        /* a plain scan reports YT_SCAN_PATH_PROJ_COMPACT or nothing */
+        t_last_scan_path = 0;
         if (plan->order_count > 0) {
             /* scan + ORDER BY ... LIMIT: k-selection, no full materialization */
             return run_scan_topk(plan, chunk, options, &dp, &SP, jd, jd2,

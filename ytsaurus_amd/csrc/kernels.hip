@@ -692,6 +692,32 @@ __device__ __noinline__ DVal str_pred_row(const DevPlan& p, const ColCtx& c, con
     return v;
 }
 
+/* P_STR_REF: the row's value of a projected STRING column, as a reference to
+ * its entry (common.h). Out of line for the reason given at str_pred_row. */
+__device__ __noinline__ DVal str_ref_row(const DevPlan& p, const ColCtx& c, const PInst& in)
+{
+    const int off = c.col_seg_off[in.col];
+    int lo;
+    if (p.col_uniform_shift[in.col]) {
+        lo = (int)(c.row >> p.col_uniform_shift[in.col]);
+    } else {
+        int hi = c.col_seg_cnt[in.col];
+        lo = 0;
+        while (lo + 1 < hi) {
+            int mid = (lo + hi) / 2;
+            if (c.segs[off + mid].start_row <= c.row) lo = mid;
+            else hi = mid;
+        }
+    }
+    const DevSeg& s = c.segs[off + lo];
+    const uint64_t id = str_key_id(s, c.segex[off + lo], c.row - s.start_row);
+    DVal v;
+    v.type = YT_VT_STRING;
+    v.null_ = id == 0;
+    v.bits = id ? (((uint64_t)(off + lo) << 32) | (id - 1)) : 0;
+    return v;
+}
+
 __device__ DVal eval_prog(const DevPlan& p, ColCtx& c, int off, int len)
 {
     DVal stk[12];
@@ -725,6 +751,9 @@ __device__ DVal eval_prog(const DevPlan& p, ColCtx& c, int off, int len)
         }
         case P_STR_PRED:
             stk[sp++] = str_pred_row(p, c, in);
+            break;
+        case P_STR_REF:
+            stk[sp++] = str_ref_row(p, c, in);
             break;
         default: {
             DVal b = stk[--sp];
@@ -3212,6 +3241,230 @@ k_strpred_entries(const DevSeg* segs, const SegEx* segex, int seg_off, int nsegs
     }
 }
 
+/* ------------------------------------------------------------------ */
+/* scan + project with STRING projections: stable device compaction of  */
+/* one window and the byte gather (common.h ProjTot, StrGatherRec).     */
+/* k_scan_project has left out[r * np + pj] and pass[r]; a string value */
+/* holds its entry reference (P_STR_REF). Reduce-then-scan in three     */
+/* launches — no workgroup ever waits on another:                       */
+/*   k_proj_tile_totals  lengths into pad_, {rows, bytes} per tile      */
+/*   k_proj_scan_tiles   one workgroup: exclusive scan of the tile      */
+/*                       totals, looping over them 256 at a time        */
+/*   k_proj_scatter      per-tile rescan; survivors written densely in  */
+/*                       row order, one gather record per string slot   */
+/* A thread owns 8 CONSECUTIVE rows of its tile, so thread order is row */
+/* order and the scan is stable by construction.                        */
+
+constexpr int kProjRowsPerThread = kProjTile / 256;
+
+/* exclusive scan of (a, b) over the 256 threads of a block, in thread
+ * order; *ta, *tb = the block totals (the same in every thread) */
+__device__ __forceinline__ void block_excl_scan2(uint64_t& a, uint64_t& b,
+                                                 uint64_t* ta, uint64_t* tb,
+                                                 uint64_t (*wsum)[2] /* [4] LDS */)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t ia = a, ib = b;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t xa = (uint64_t)__shfl_up((unsigned long long)ia, d, 64);
+        const uint64_t xb = (uint64_t)__shfl_up((unsigned long long)ib, d, 64);
+        if (lane >= d) { ia += xa; ib += xb; }
+    }
+    __syncthreads();            /* wsum may still be read from the last call */
+    if (lane == 63) { wsum[wave][0] = ia; wsum[wave][1] = ib; }
+    __syncthreads();
+    uint64_t ba = 0, bb = 0, sa = 0, sb = 0;
+    for (int w = 0; w < 4; w++) {
+        if (w < wave) { ba += wsum[w][0]; bb += wsum[w][1]; }
+        sa += wsum[w][0];
+        sb += wsum[w][1];
+    }
+    a = ba + ia - a;
+    b = bb + ib - b;
+    *ta = sa;
+    *tb = sb;
+}
+
+/* length of the entry a P_STR_REF value points at */
+__device__ __forceinline__ uint32_t str_ref_len(const DevSeg* segs, const SegEx* segex,
+                                                uint64_t ref)
+{
+    const uint32_t seg = (uint32_t)(ref >> 32);
+    uint32_t len;
+    (void)dict_entry(segs[seg], segex[seg], (int64_t)(ref & 0xFFFFFFFFu), &len);
+    return len;
+}
+
+__global__ void __launch_bounds__(256)
+k_proj_tile_totals(const DevSeg* segs, const SegEx* segex, DevOutVal* out,
+                   const uint8_t* pass, int64_t row_count, int np,
+                   unsigned str_mask, ProjTot* tile_tot)
+{
+    __shared__ uint64_t wsum[4][2];
+    const int64_t r0 = (int64_t)blockIdx.x * kProjTile
+                     + (int64_t)threadIdx.x * kProjRowsPerThread;
+    uint64_t rows = 0, bytes = 0;
+    for (int i = 0; i < kProjRowsPerThread; i++) {
+        const int64_t r = r0 + i;
+        if (r >= row_count || !pass[r]) continue;
+        rows++;
+        for (int pj = 0; pj < np; pj++) {
+            if (!((str_mask >> pj) & 1)) continue;
+            DevOutVal& o = out[r * np + pj];
+            if (o.type != YT_VT_STRING) continue;
+            const uint32_t len = str_ref_len(segs, segex, o.bits);
+            o.pad_ = len;
+            bytes += len;
+        }
+    }
+    uint64_t ta, tb;
+    block_excl_scan2(rows, bytes, &ta, &tb, wsum);
+    if (threadIdx.x == 0) {
+        tile_tot[blockIdx.x].rows = ta;
+        tile_tot[blockIdx.x].bytes = tb;
+    }
+}
+
+/* ONE workgroup. tile_tot becomes the exclusive prefix, in place;
+ * totals[0] = {all rows, all bytes} of the window. */
+__global__ void __launch_bounds__(256)
+k_proj_scan_tiles(ProjTot* tile_tot, int ntiles, ProjTot* totals)
+{
+    __shared__ uint64_t wsum[4][2];
+    uint64_t ca = 0, cb = 0;            /* carry: uniform across the block */
+    for (int base = 0; base < ntiles; base += 256) {
+        const int i = base + (int)threadIdx.x;
+        uint64_t a = 0, b = 0;
+        if (i < ntiles) { a = tile_tot[i].rows; b = tile_tot[i].bytes; }
+        uint64_t ta, tb;
+        block_excl_scan2(a, b, &ta, &tb, wsum);
+        if (i < ntiles) {
+            tile_tot[i].rows = ca + a;
+            tile_tot[i].bytes = cb + b;
+        }
+        ca += ta;
+        cb += tb;
+    }
+    if (threadIdx.x == 0) { totals[0].rows = ca; totals[0].bytes = cb; }
+}
+
+/* Survivors to cout[(dense row) * np + pj], in input row order. A string
+ * value becomes bits = byte offset in the window pool, pad_ = length; every
+ * string slot of a surviving row gets record (dense row) * nstr + (rank of
+ * pj among the string projections), a null one with len 0. */
+__global__ void __launch_bounds__(256)
+k_proj_scatter(const DevOutVal* out, const uint8_t* pass, int64_t row_count,
+               int np, unsigned str_mask, int nstr, const ProjTot* tile_off,
+               DevOutVal* cout, StrGatherRec* recs)
+{
+    __shared__ uint64_t wsum[4][2];
+    const int64_t r0 = (int64_t)blockIdx.x * kProjTile
+                     + (int64_t)threadIdx.x * kProjRowsPerThread;
+    uint64_t rows = 0, bytes = 0;
+    for (int i = 0; i < kProjRowsPerThread; i++) {
+        const int64_t r = r0 + i;
+        if (r >= row_count || !pass[r]) continue;
+        rows++;
+        for (int pj = 0; pj < np; pj++) {
+            if (!((str_mask >> pj) & 1)) continue;
+            const DevOutVal& o = out[r * np + pj];
+            if (o.type == YT_VT_STRING) bytes += o.pad_;
+        }
+    }
+    uint64_t ta, tb;
+    block_excl_scan2(rows, bytes, &ta, &tb, wsum);
+    uint64_t drow = tile_off[blockIdx.x].rows + rows;
+    uint64_t dbyte = tile_off[blockIdx.x].bytes + bytes;
+    for (int i = 0; i < kProjRowsPerThread; i++) {
+        const int64_t r = r0 + i;
+        if (r >= row_count || !pass[r]) continue;
+        int sidx = 0;
+        for (int pj = 0; pj < np; pj++) {
+            DevOutVal o = out[r * np + pj];
+            if ((str_mask >> pj) & 1) {
+                StrGatherRec g;
+                g.ref = kStrRefNull;
+                g.dst = 0;
+                g.len = 0;
+                g.pad_ = 0;
+                if (o.type == YT_VT_STRING) {
+                    g.ref = o.bits;
+                    g.dst = dbyte;
+                    g.len = o.pad_;
+                    o.bits = dbyte;
+                    dbyte += o.pad_;
+                }
+                recs[drow * nstr + sidx] = g;
+                sidx++;
+            }
+            cout[drow * np + pj] = o;
+        }
+        drow++;
+    }
+}
+
+/* lengths for host-built records (scan + ORDER BY): len from ref */
+__global__ void __launch_bounds__(256)
+k_str_reclen(const DevSeg* segs, const SegEx* segex, StrGatherRec* recs, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t ref = recs[i].ref;
+    recs[i].len = ref == kStrRefNull ? 0 : str_ref_len(segs, segex, ref);
+}
+
+/* Byte gather: record i's entry bytes -> pool[dst, dst + len). One wave64
+ * per 64 records. When every length in the wave is at most kGatherSmall each
+ * lane copies its own string; otherwise the wave takes the records one at a
+ * time, pointer and length broadcast by __shfl, all 64 lanes copying
+ * lane-strided — a multi-KB string is 64 bytes per step instead of one lane's
+ * serial loop, and the byte accesses of one step share cache lines. Plain
+ * byte loads and stores: source and destination alignments are unrelated.
+ * A record that would end past pool_bytes is skipped (cannot happen for
+ * records whose dst came from a prefix sum of these same lengths). */
+constexpr uint32_t kGatherSmall = 32;
+
+__global__ void __launch_bounds__(256)
+k_str_gather(const DevSeg* segs, const SegEx* segex, const StrGatherRec* recs,
+             int64_t n, char* pool, uint64_t pool_bytes)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t wstride = (int64_t)gridDim.x * 4;
+    const int64_t nwaves = (n + 63) / 64;
+    for (int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); w < nwaves;
+         w += wstride) {
+        const int64_t i = w * 64 + lane;
+        uint32_t len = 0;
+        const char* src = nullptr;
+        char* dst = nullptr;
+        if (i < n) {
+            const StrGatherRec g = recs[i];
+            if (g.ref != kStrRefNull && g.len &&
+                g.dst + g.len <= pool_bytes) {
+                const uint32_t seg = (uint32_t)(g.ref >> 32);
+                uint32_t elen;
+                src = dict_entry(segs[seg], segex[seg],
+                                 (int64_t)(g.ref & 0xFFFFFFFFu), &elen);
+                len = g.len < elen ? g.len : elen;
+                dst = pool + g.dst;
+            }
+        }
+        if (!__any(len > kGatherSmall)) {
+            for (uint32_t b = 0; b < len; b++) dst[b] = src[b];
+            continue;
+        }
+        for (int k = 0; k < 64; k++) {
+            const uint32_t kl = (uint32_t)__shfl((int)len, k, 64);
+            if (!kl) continue;                         /* wave-uniform */
+            const char* ks = (const char*)(uintptr_t)
+                __shfl((unsigned long long)(uintptr_t)src, k, 64);
+            char* kd = (char*)(uintptr_t)
+                __shfl((unsigned long long)(uintptr_t)dst, k, 64);
+            for (uint32_t b = lane; b < kl; b += 64) kd[b] = ks[b];
+        }
+    }
+}
+
 /* G1: per row — filter, aggregate arguments (eval_prog), then
  * agg_update_slot into the row's record
  *   acc[stride * (acc_base[seg] + id-1)] = { rows, {bits, nonnull} per agg }
@@ -4227,6 +4480,56 @@ hipError_t ytql_launch_scan_project(const DevPlan* p, const DevSeg* segs,
     hipLaunchKernelGGL(k_scan_project, dim3(grid), dim3(block), 0, st,
                        *p, segs, segex, col_seg_off, col_seg_cnt, row_base,
                        row_count, *jd, *jd2, out, pass, error_out);
+    return hipGetLastError();
+}
+
+/* the two reduce-then-scan launches over one scan+project window: per-tile
+ * totals, then the scan of the tile totals (tile_tot needs
+ * ceil(row_count / kProjTile) entries; totals one) */
+hipError_t ytql_launch_proj_offsets(const DevSeg* segs, const SegEx* segex,
+                                    DevOutVal* out, const uint8_t* pass,
+                                    int64_t row_count, int np, unsigned str_mask,
+                                    ProjTot* tile_tot, ProjTot* totals,
+                                    hipStream_t st)
+{
+    const int ntiles = (int)((row_count + kProjTile - 1) / kProjTile);
+    hipLaunchKernelGGL(k_proj_tile_totals, dim3(ntiles), dim3(256), 0, st,
+                       segs, segex, out, pass, row_count, np, str_mask, tile_tot);
+    hipLaunchKernelGGL(k_proj_scan_tiles, dim3(1), dim3(256), 0, st,
+                       tile_tot, ntiles, totals);
+    return hipGetLastError();
+}
+
+hipError_t ytql_launch_proj_scatter(const DevOutVal* out, const uint8_t* pass,
+                                    int64_t row_count, int np, unsigned str_mask,
+                                    int nstr, const ProjTot* tile_off,
+                                    DevOutVal* cout, StrGatherRec* recs,
+                                    hipStream_t st)
+{
+    const int ntiles = (int)((row_count + kProjTile - 1) / kProjTile);
+    hipLaunchKernelGGL(k_proj_scatter, dim3(ntiles), dim3(256), 0, st,
+                       out, pass, row_count, np, str_mask, nstr, tile_off,
+                       cout, recs);
+    return hipGetLastError();
+}
+
+hipError_t ytql_launch_str_reclen(const DevSeg* segs, const SegEx* segex,
+                                  StrGatherRec* recs, int64_t n, hipStream_t st)
+{
+    const int grid = (int)((n + 255) / 256);
+    hipLaunchKernelGGL(k_str_reclen, dim3(grid), dim3(256), 0, st,
+                       segs, segex, recs, n);
+    return hipGetLastError();
+}
+
+hipError_t ytql_launch_str_gather(const DevSeg* segs, const SegEx* segex,
+                                  const StrGatherRec* recs, int64_t n,
+                                  char* pool, uint64_t pool_bytes, hipStream_t st)
+{
+    const int64_t want = (n + 255) / 256;       /* 4 waves of 64 records */
+    const int grid = (int)(want > 8192 ? 8192 : (want > 0 ? want : 1));
+    hipLaunchKernelGGL(k_str_gather, dim3(grid), dim3(256), 0, st,
+                       segs, segex, recs, n, pool, pool_bytes);
     return hipGetLastError();
 }
 
