@@ -513,6 +513,12 @@ enum {
 };
 uint32_t yt_gpu_debug_last_scan_path(void);
 
+/* Diagnostic only: rows per tile of the partitioned GROUP BY's first phase;
+ * large != 0: the tile of 8-byte packed records once a record region holds
+ * that many. Compile-time constants of the library; tests size their inputs
+ * around them. */
+int32_t yt_gpu_debug_partition_tile_rows(int large);
+
 /* Diagnostic only: dictionary entries (runs / rows for the direct layouts)
  * on which the calling thread's last query evaluated string predicates,
  * summed over its predicates; 0 when it had none. */

@@ -227,6 +227,9 @@ struct OutGroup {
  * aggs: sum(direct col) and/or sum(1). */
 struct FastShape {
     int32_t valid;
+    int32_t ragged;           /* the shape fits but segment row counts differ:
+                                 the partitioned path only (its tiles are
+                                 masked per segment), never k_scan_fast */
     int32_t filter_col;       /* -1 = none */
     int64_t filter_lo, filter_hi;   /* inclusive */
     int32_t key_col;          /* -1 = global */
@@ -261,69 +264,62 @@ struct FastParams {
 };
 
 /* two-phase partitioned group-by (BASELINE configs 3/4 family):
- * Phase A (k_scan_partition): fused decode+filter, hash-partition rows into
- * kNB buckets as 16-byte {key,val} records (mirrors the reference's
- * in-process shuffle partition, shuffling_reader.cpp:40-42, pushed down to
- * the row level so aggregation can run in LDS).
- * Phase B (k_bucket_agg): one workgroup per bucket aggregates its records
- * in an LDS open-addressing table and emits compacted OutGroups. */
+ * Phase A (k_scan_partition): fused decode+filter; every row is decoded once
+ * into an 8-byte packed or 16-byte {key,val} record and partitioned into kNB
+ * buckets (mirrors the reference's in-process shuffle partition,
+ * shuffling_reader.cpp:40-42, pushed down to the row level so aggregation
+ * can run in LDS). A workgroup gathers a tile's records bucket-major in an
+ * LDS scratch and copies each bucket's run out as contiguous stores.
+ * Phase B (k_bucket_agg / k_bucket_agg_direct): one workgroup per bucket
+ * aggregates its records in an LDS table and emits compacted OutGroups. */
 constexpr int kNB = 1024;          /* partition buckets */
 constexpr int kHSlots = 2048;      /* LDS table slots per bucket (48 KB -> 3 WGs/CU) */
 constexpr uint64_t kEmptyKey = 0x8000000000000000ULL;  /* INT64_MIN bits */
 
+/* phase-A geometry: a thread holds up to 16 rows of a tile (8 with 16-byte
+ * records), a compile-time constant so the tile's records and (bucket, rank)
+ * words stay in registers. Either way a tile's records fill a 64 KiB LDS
+ * scratch; with the three kNB-word histograms that is 76 KiB, two
+ * 512-thread workgroups per CU.
+ * A (bucket, XCD sub) region must hold one whole tile whatever the key skew
+ * (bucket_stride's fixed slack is 4096 records for that reason), so packed
+ * records tile kPartTileMax rows only once bucket_stride reaches that, and
+ * kPartTileMin below; the kernel masks the rows a tile does not use. */
+constexpr int kPartThreads = 512;
+constexpr int kPartTileMax = 16 * kPartThreads;    /* packed records, large inputs */
+constexpr int kPartTileMin = 8 * kPartThreads;     /* 16-byte records; small inputs */
+constexpr size_t kPartScratchBytes = (size_t)kPartTileMax * 8;
+constexpr size_t kPartLdsBytes = kPartScratchBytes + 3 * kNB * 4 + 64;
+
 struct PartParams {
-    int32_t tile_rows;
-    int32_t tiles_per_seg;
+    int32_t tile_rows;            /* kPartTileMax or kPartTileMin */
+    int32_t tiles_per_seg;        /* the rows, or whole tiles, past a segment's
+                                     end are masked */
     int32_t ntiles;
     int32_t filter_idx;           /* used-col index; -1 none */
     int32_t key_idx;              /* used-col index (required) */
     int32_t val_idx;              /* used-col index of the sum arg; -1 none */
     int32_t nused;
-    int32_t has_val_nulls;
+    int32_t has_val_nulls;        /* value-null rows go to the null stream */
     int32_t has_key_nulls;
+    int32_t has_filter_nulls;
     int32_t sum_slot;             /* agg slot of the sum; -1 none */
     int32_t agg_count;
-    int32_t pad_;
     int64_t filter_lo, filter_hi;
-    int64_t bucket_stride;        /* record capacity per bucket */
-    int64_t nbucket_stride;       /* null-stream capacity per bucket */
+    int64_t bucket_stride;        /* record capacity per (bucket, XCD sub) region */
+    int64_t nbucket_stride;       /* null-stream capacity per region */
     /* 8-byte packed records: when the key and value zigzag spans fit 64
      * bits together, a record is (kzz - gmin_k) | (vzz - gmin_v) << bits_k
      * — half the partition traffic of {key,val} pairs. */
     int32_t packed_mode;
     int32_t bits_k;
     uint64_t gmin_k, gmin_v;
-    int32_t stage_bm_mask;        /* bit u: stage used-col u's null bitmap */
-    int32_t has_filter_nulls;
-    int32_t stage_val;            /* stage the value column's packed words too */
     /* direct-span mode (small key zigzag span): buckets are key-RANGE
      * slices (bucket = krel >> dshift) and phase B indexes an LDS array
-     * directly — no hash probe, no CAS, no stored keys. */
+     * directly — no hash probe, no CAS, no stored keys. The copy-out of
+     * phase A re-derives a record's bucket the same way. */
     int32_t direct_mode;
     int32_t dshift;               /* per-bucket key-slot range = 1 << dshift */
-    /* LDS bucket-major reorder: pass 2 writes records into an LDS scratch
-     * (dense bucket-major within the tile), then a copy phase streams each
-     * bucket run to its aligned global claim — every HBM line of the record
-     * stream is written whole, by coalesced adjacent-lane stores (the 8B
-     * scatter wrote 45 GB for 8 GB of records: partial lines evicted from
-     * L2 between stores). Packed records, no val-null stream only. */
-    int32_t reorder;
-    int32_t store_mode;           /* 0 plain, 1 sc1 write-through, 2 no store (timing floor probe) */
-    /* per-WORKGROUP record regions: region = bucket * gridDim + blockIdx,
-     * appended locally (LDS running base, init once per WG) — the per-tile
-     * global cursor reserve was ~1 atomic per 4 rows (250M global atomics
-     * per 1B-row query vs the ~30 G/s chip ceiling = ~8 ms of the pass).
-     * cursors[] becomes the per-(bucket,wg) final counts, published at WG
-     * end. Requires !has_val_nulls (the null stream keeps 8 XCD subs). */
-    int32_t wg_streams;
-    /* 64B-aligned record claims: each (tile,bucket) reserves a multiple of 8
-     * records and fills the tail with pad records, so every HBM line of the
-     * partition stream is written whole by one workgroup within one tile
-     * pass (round-1 PMC: unaligned 8B scatter wrote 42 GB for 8 GB of
-     * records). Pads: packed records use bit 63; 16B/null-stream records
-     * use key == kEmptyKey (real INT64_MIN keys never enter the streams —
-     * they are side-slotted). */
-    int32_t aligned;
 };
 
 /* string-keyed GROUP BY (BASELINE config 5 family): dictionary-encoded

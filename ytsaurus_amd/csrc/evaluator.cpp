@@ -35,12 +35,12 @@ hipError_t ytql_launch_scan_zzrange(const DevSeg*, const SegEx*, int, int, int,
 hipError_t ytql_launch_scan_partition(const PartParams*, const DevSeg*, const SegEx*,
                                       const FastCol*, TableHdr*, unsigned long long*,
                                       void*, unsigned long long*, uint64_t*,
-                                      size_t, int, hipStream_t);
+                                      int, hipStream_t);
 hipError_t ytql_launch_bucket_agg(const void*, const unsigned long long*, int64_t,
                                   const uint64_t*, const unsigned long long*, int64_t,
                                   OutGroup*, unsigned long long*, int64_t,
                                   TableHdr*, int, int, int, int,
-                                  uint64_t, uint64_t, int, int, hipStream_t);
+                                  uint64_t, uint64_t, int, hipStream_t);
 hipError_t ytql_launch_bucket_agg_direct(const void*, const unsigned long long*, int64_t,
                                          const uint64_t*, const unsigned long long*, int64_t,
                                          OutGroup*, unsigned long long*, int64_t,
@@ -888,18 +888,21 @@ static void analyze_fast(const YtPlan* plan, const YtChunk* chunk, FastShape* fs
         types[c] = (uint8_t)chunk->columns[c].value_type;
     ct = types;
 
-    /* all segments of all columns must be DirectDense int64, uniform interior
-     * row counts */
+    /* all segments of all columns must be DirectDense int64 and cut at the
+     * same rows; k_scan_fast also needs uniform interior row counts, the
+     * partitioned path masks its tiles per segment and takes any (ragged) */
     int32_t seg_cnt0 = chunk->columns[0].segment_count;
     int32_t rows0 = seg_cnt0 ? chunk->columns[0].segments[0].row_count : 0;
+    bool ragged = false;
     for (int c = 0; c < chunk->column_count; c++) {
         const YtColumn& col = chunk->columns[c];
         if (col.value_type != YT_VT_INT64) return;
         if (col.segment_count != seg_cnt0) return;
         for (int s = 0; s < col.segment_count; s++) {
             if (col.segments[s].type != YT_SEG_DIRECT_DENSE) return;
-            if (s < col.segment_count - 1 && col.segments[s].row_count != rows0) return;
-            if (col.segments[s].row_count > rows0) return;
+            if (col.segments[s].row_count != chunk->columns[0].segments[s].row_count) return;
+            if (s < col.segment_count - 1 && col.segments[s].row_count != rows0) ragged = true;
+            if (col.segments[s].row_count > rows0) ragged = true;
         }
     }
     if (seg_cnt0 == 0) return;
@@ -945,7 +948,8 @@ static void analyze_fast(const YtPlan* plan, const YtChunk* chunk, FastShape* fs
     if (fs->nsum == 0 && fs->filter_col < 0 && fs->key_col < 0) {
         return;   /* pure row count with no staged column — generic path */
     }
-    fs->valid = 1;
+    fs->valid = ragged ? 0 : 1;
+    fs->ragged = ragged ? 1 : 0;
 }
 
 /* ------------------------------------------------------------------ */
@@ -1133,6 +1137,11 @@ static thread_local uint32_t t_last_scan_path = 0;
 extern "C" uint32_t yt_gpu_debug_last_scan_path(void)
 {
     return t_last_scan_path;
+}
+
+extern "C" int32_t yt_gpu_debug_partition_tile_rows(int large)
+{
+    return large ? kPartTileMax : kPartTileMin;
 }
 
 static uint64_t next_pow2(uint64_t x)
@@ -1386,10 +1395,6 @@ static int run_partitioned(const YtPlan* plan, const YtChunk* chunk,
     pp.has_key_nulls = (R->col_null_flags[fs->key_col] != 0);
     pp.has_val_nulls = pp.val_idx >= 0 && (R->col_null_flags[fs->sum_col[0]] != 0);
     pp.has_filter_nulls = pp.filter_idx >= 0 && (R->col_null_flags[fs->filter_col] != 0);
-    pp.stage_bm_mask = 0;
-    for (int u = 0; u < nused; u++) {
-        if (R->col_null_flags[used[u]] != 0) pp.stage_bm_mask |= 1 << u;
-    }
 
     /* 8-byte packed records when the combined zigzag spans fit 64 bits */
     {
@@ -1437,7 +1442,7 @@ static int run_partitioned(const YtPlan* plan, const YtChunk* chunk,
         }
         /* the meta bound overstates each span by at most one bit; scan
          * exactly when that one bit could enable direct-span mode or the
-         * aligned pad bit (cheap: one streaming read of the column) */
+         * spare bit 63 it needs (cheap: one streaming read of the column) */
         if ((bk >= 1 && bk <= 23) && !(bk <= 22 && bk + bv <= 63)) {
             rc = exact_range(fs->key_col);
             if (rc != YT_OK) return rc;
@@ -1465,36 +1470,17 @@ static int run_partitioned(const YtPlan* plan, const YtChunk* chunk,
             pp.gmin_k = R->col_zzmin[fs->key_col];
             pp.gmin_v = gmin_v;
         }
-        /* aligned 64B claims need a pad encoding: bit 63 for packed records
-         * (spare iff bk+bv <= 63), kEmptyKey for 16B records (always).
-         * Pads pay off only with the LDS reorder (coalesced full-line
-         * writes); without it the 8B scatter's partial-line eviction isn't
-         * fixed and pads just inflate the stream (measured r2c_ab). */
-        int can_pad = (!pp.packed_mode || pp.bits_k + bv <= 63) ? 1 : 0;
-        /* measured slower than the plain scatter at every tile size
-         * (r2 A/Bs: 23.8-41 ms vs 18.7 ms) — L2 absorbs the 8B scatter
-         * better than any LDS round-trip; keep as an experiment knob */
-        pp.reorder = (pp.packed_mode && can_pad && !pp.has_val_nulls
-                      && getenv("YTQL_REORDER")) ? 1 : 0;
-        pp.aligned = pp.reorder;
-        {
-            const char* sm = getenv("YTQL_STORE");   /* perf experiments only */
-            if (sm) pp.store_mode = atoi(sm);
-        }
-        /* measured ~1ms slower than XCD sub-streams (phase B loses its
-         * paired-load ILP across 2048 short streams); keep as a knob */
-        {
-            const char* wgm = getenv("YTQL_WGSTREAMS");   /* 1 two-pass, 2 single-pass */
-            pp.wg_streams = (!pp.reorder && !pp.has_val_nulls && wgm)
-                ? atoi(wgm) : 0;
-            if (pp.wg_streams == 2 && !pp.packed_mode) pp.wg_streams = 1;
-        }
+        /* direct-span mode asks for bit 63 of a packed record to be spare
+         * (bk + bv <= 63; 16-byte records always qualify). The padded claims
+         * that used the bit are gone and nothing sets it any more; the
+         * condition stays only so that the mode lattice, which
+         * tests/test_partition_modes.py pins, does not move */
+        int spare_bit = (!pp.packed_mode || pp.bits_k + bv <= 63) ? 1 : 0;
         /* direct-span mode: when the key zigzag span is small, partition by
          * key RANGE and index phase B's per-bucket array directly (the
-         * headline config — 1M distinct keys — spans 21 bits). Needs the
-         * pad encoding (phase B skips by sign bit), so requires aligned. */
+         * headline config — 1M distinct keys — spans 21 bits). */
         pp.gmin_k = R->col_zzmin[fs->key_col];
-        if (bk <= 22 && can_pad && !force_hash && !getenv("YTQL_NO_DIRECT")) {
+        if (bk <= 22 && spare_bit && !force_hash && !getenv("YTQL_NO_DIRECT")) {
             pp.direct_mode = 1;
             pp.dshift = bk > 10 ? bk - 10 : 0;
             if (tried_direct) *tried_direct = true;
@@ -1509,72 +1495,36 @@ static int run_partitioned(const YtPlan* plan, const YtChunk* chunk,
     int64_t rows = chunk->row_count;
     if (options->input_row_limit > 0 && options->input_row_limit < rows)
         rows = options->input_row_limit;
-    int32_t seg0_rows = R->h_segs[R->h_off[fs->key_col]].row_count;
 
-    /* LDS: 4*kNB u32 histogram structures + staged columns (value column's
-     * packed words are NOT staged — read from global in the write pass) */
-    unsigned w = maxw ? maxw : 1;
-    /* bigger tiles make aligned claims cheaper (fewer pad tails per
-     * bucket); bounded by LDS (key staging) at 2 workgroups/CU (<=80KB) */
-    /* reorder: 31x256 rows -> scratch 62KB + 16KB histograms = 2 WGs/CU
-     * (8192 would land 32 bytes over the 80KB half-LDS line).
-     * Scatter mode: 4096 measured best (27KB LDS -> 5 WGs/CU; the kernel is
-     * 73% WAIT_ANY, occupancy is the lever — r2 tile sweeps). */
-    int tile_rows = pp.reorder ? 7936 : 4096;
-    bool tile_forced = false;
-    {
-        const char* ev = getenv("YTQL_TILE");   /* perf experiments only */
-        if (ev && atoi(ev) >= 256) { tile_rows = atoi(ev); tile_forced = true; }
-        if (tile_rows > 16384) tile_rows = 16384;   /* per-thread row arrays bound */
-    }
-    /* LDS: per-tile bucket histograms + the staged key column */
-    auto lds_for = [&](int tr) {
-        /* reorder mode: record scratch instead of the staged key column;
-         * wg single-pass: histograms only (keys read once, from global) */
-        if (pp.reorder)
-            return (size_t)tr * 8 + (size_t)4 * kNB * 4 + 64;
-        if (pp.wg_streams == 2)
-            return (size_t)4 * kNB * 4 + 256;
-        return (size_t)4 * kNB * 4 + ((size_t)tr * w / 64 + 2) * 8 + 256;
-    };
-    size_t lds = lds_for(tile_rows);
-    while (!tile_forced && lds > 80 * 1024 && tile_rows > 4096) { tile_rows >>= 1; lds = lds_for(tile_rows); }
-    while (lds > 158 * 1024 && tile_rows > 1024) { tile_rows >>= 1; lds = lds_for(tile_rows); }
-    while (tile_rows > 256 && tile_rows > seg0_rows) tile_rows >>= 1;
-    lds = lds_for(tile_rows);
+    const int nsub = 8;
+    /* per (bucket, XCD) sub-streams: 8x more cursors, 1/8 the rows each */
+    pp.bucket_stride = rows / (kNB * 8) + (rows / (kNB * 8)) / 2 + 4096;
+    pp.bucket_stride = (pp.bucket_stride + 7) & ~(int64_t)7;
+    pp.nbucket_stride = pp.has_val_nulls ? pp.bucket_stride : 0;
+
+    /* a region holds one whole tile whatever the key skew (common.h); a
+     * segment takes as many tiles as its longest sibling needs, and the
+     * kernel masks the rows, or whole tiles, past its end */
+    const int tile_rows = (pp.packed_mode && pp.bucket_stride >= kPartTileMax)
+        ? kPartTileMax : kPartTileMin;
     pp.tile_rows = tile_rows;
-    pp.tiles_per_seg = (seg0_rows + tile_rows - 1) / tile_rows;
+    const int nseg = R->h_cnt[fs->key_col];
+    int32_t max_seg_rows = 1;
+    for (int s = 0; s < nseg; s++)
+        max_seg_rows = std::max(max_seg_rows, R->h_segs[R->h_off[fs->key_col] + s].row_count);
+    pp.tiles_per_seg = (max_seg_rows + tile_rows - 1) / tile_rows;
     {
-        int nseg = R->h_cnt[fs->key_col];
         int32_t last_rows = R->h_segs[R->h_off[fs->key_col] + nseg - 1].row_count;
         pp.ntiles = (nseg - 1) * pp.tiles_per_seg + (last_rows + tile_rows - 1) / tile_rows;
     }
+    /* two workgroups fit a CU; a grid of 512, 1024 or 2048 measured alike
+     * (YTQL_GRID: sweeps only) */
     int grid = pp.ntiles < 2048 ? (pp.ntiles ? pp.ntiles : 1) : 2048;
     {
         const char* gv = getenv("YTQL_GRID");   /* perf experiments only */
         if (gv && atoi(gv) >= 8 && atoi(gv) < grid) grid = atoi(gv) & ~7;
         if (grid < 1) grid = 1;
     }
-    int nsub = pp.wg_streams ? grid : 8;
-    if (pp.wg_streams) {
-        /* per-(bucket, WG) regions: rows this WG scans / kNB + skew slack */
-        int64_t tiles_per_wg = (pp.ntiles + grid - 1) / grid;
-        int64_t rows_per_wg = tiles_per_wg * pp.tile_rows;
-        pp.bucket_stride = rows_per_wg / kNB + (rows_per_wg / kNB) / 2 + 64;
-    } else {
-        /* per (bucket, XCD) sub-streams: 8x more cursors, 1/8 the rows each.
-         * Aligned mode adds up to 7 pad records per (tile,bucket,sub) claim —
-         * budget the expected pad tail (~3.5 per claiming tile) explicitly. */
-        pp.bucket_stride = rows / (kNB * 8) + (rows / (kNB * 8)) / 2 + 4096;
-        if (pp.aligned) {
-            int64_t tiles_per_sub = ((int64_t)pp.tiles_per_seg * R->h_cnt[fs->key_col] + 7) / 8;
-            pp.bucket_stride += 4 * tiles_per_sub + 4096;
-        }
-    }
-    /* every (bucket,sub) region must start 64B-aligned or aligned claims
-     * land mid-line and every run straddles lines */
-    pp.bucket_stride = (pp.bucket_stride + 7) & ~(int64_t)7;
-    pp.nbucket_stride = pp.has_val_nulls ? pp.bucket_stride : 0;
 
     std::vector<FastCol> fc(nused);
     for (int u = 0; u < nused; u++) {
@@ -1618,7 +1568,7 @@ static int run_partitioned(const YtPlan* plan, const YtChunk* chunk,
         HIP_CHECK(ytql_launch_scan_partition(&pp, R->d_segs, R->d_segex, R->d_fastcols,
                                              R->d_th, R->d_cursors, R->d_recs,
                                              R->d_ncursors, R->d_nrecs,
-                                             lds, grid, R->stream));
+                                             grid, R->stream));
         HIP_CHECK(hipEventRecord(ev1, R->stream));
         if (pp.direct_mode) {
             HIP_CHECK(ytql_launch_bucket_agg_direct(R->d_recs, R->d_cursors, pp.bucket_stride,
@@ -1633,7 +1583,7 @@ static int run_partitioned(const YtPlan* plan, const YtChunk* chunk,
                                              R->d_groups, R->d_counter, cap_groups,
                                              R->d_th, pp.sum_slot, pp.agg_count,
                                              pp.packed_mode, pp.bits_k,
-                                             pp.gmin_k, pp.gmin_v, pp.aligned, nsub, R->stream));
+                                             pp.gmin_k, pp.gmin_v, nsub, R->stream));
         }
         HIP_CHECK(hipEventRecord(ev2, R->stream));
         HIP_CHECK(hipStreamSynchronize(R->stream));
@@ -1693,7 +1643,7 @@ static int run_scan(const YtPlan* plan, const YtChunk* chunk,
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool partitioned = false;
 
-    if (fs->valid && fs->key_col >= 0 && fs->nsum <= 1) {
+    if ((fs->valid || fs->ragged) && fs->key_col >= 0 && fs->nsum <= 1) {
         bool done = false;
         partitioned = true;
         bool tried_direct = false;
@@ -4563,7 +4513,7 @@ extern "C" int yt_gpu_query_execute(
     /* a string predicate runs in the interpreter only. analyze_fast refuses
      * any chunk that holds a non-int64 column, so this never fires; it is
      * stated so that it does not depend on that */
-    if (SP.any) fs.valid = 0;
+    if (SP.any) fs.valid = fs.ragged = 0;
 
     DeviceRun R;
     R.stream = (hipStream_t)(uintptr_t)options->stream;
@@ -4737,7 +4687,7 @@ static int query_partial_impl(
     if (rc) return rc;
     FastShape fs;
     analyze_fast(plan, chunk, &fs);
-    if (SP.any) fs.valid = 0;     /* interpreter only, as in yt_gpu_query_execute */
+    if (SP.any) fs.valid = fs.ragged = 0;   /* interpreter only, as in yt_gpu_query_execute */
 
     DeviceRun R;
     R.stream = (hipStream_t)(uintptr_t)options->stream;

@@ -22,6 +22,7 @@
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include "common.h"
 #include "strpred.h"
 #include "../../include/ytql_gpu.h"
@@ -344,7 +345,7 @@ __global__ void k_parse_segments(const DevSeg* segs, int nsegs, SegEx* out,
 /* exact zigzag-space min/max of one DirectDense int64 column (non-null
  * values): k_parse_segments' meta-only bound rounds every segment up to
  * min_value + 2^w - 1, which can overstate the span by one bit — enough to
- * disable packed records / aligned claims / direct-span mode on data that
+ * disable packed records / direct-span mode on data that
  * actually fits (the headline config: 21+41 = 62 real bits, 22+42 = 64 by
  * meta). One workgroup per segment; out[0] = min (init ~0), out[1] = max
  * (init 0). */
@@ -1965,31 +1966,51 @@ k_scan_fast(FastParams fp, const DevSeg* segs, const SegEx* segex,
 /* ------------------------------------------------------------------ */
 /* two-phase partitioned group-by (see common.h PartParams)            */
 
-__global__ void __launch_bounds__(256)
+__device__ __forceinline__ uint64_t zz_enc64(int64_t v)
+{
+    return ((uint64_t)v << 1) ^ (uint64_t)(v >> 63);
+}
+
+/* per-row state word of k_scan_partition: bucket in bits 0..9, rank within
+ * the tile's bucket run in bits 10..23, class in the top bits */
+constexpr unsigned kRowInvalid = 0xFFFFFFFFu;   /* masked, filtered out, or done */
+constexpr unsigned kRowSide = 0x80000000u;      /* | side (bit 0) | val_null << 1 */
+constexpr unsigned kRowNullVal = 0x40000000u;   /* goes to the null-value stream */
+
+/* Phase A. Canonical column slots: 0 = filter, 1 = key, 2 = value.
+ * A tile is R rows per thread, R a compile-time constant, so the decoded
+ * records and their (bucket, rank) words stay in registers and every row is
+ * decoded ONCE, straight from global memory:
+ *   1. zero the per-tile histograms;
+ *   2. decode all R rows (loads first, rows past the segment end masked),
+ *      then rank each row in its bucket with a returning LDS add;
+ *   3. one block scan of the histogram gives each bucket's offset in the
+ *      tile, one global add per non-empty bucket reserves its run in the
+ *      (bucket, XCD sub) region;
+ *   4. records go to an LDS scratch at off[b] + rank, bucket-major;
+ *   5. the scratch is copied out with every lane busy: lane r re-derives
+ *      its record's bucket and stores to base[b] + (r - off[b]), so a
+ *      bucket's run leaves as contiguous stores from adjacent lanes.
+ * Null-value rows (key only, rare) go straight to their own stream. */
+template <bool PACKED>
+__global__ void __launch_bounds__(kPartThreads, 4)
 k_scan_partition(PartParams pp, const DevSeg* segs, const SegEx* segex,
                  const FastCol* cols, TableHdr* th,
-                 unsigned long long* cursors,        /* kNB main */
+                 unsigned long long* cursors,        /* kNB x 8 main */
                  ulonglong2* recs,
-                 unsigned long long* ncursors,       /* kNB null-value stream */
+                 unsigned long long* ncursors,       /* kNB x 8 null-value stream */
                  uint64_t* nrecs)
 {
-    /* Canonical column slots: 0 = filter, 1 = key, 2 = value.
-     * Values are decoded straight from global memory (branchless funnel;
-     * the twice-read key column is staged in LDS); LDS otherwise holds only
-     * the per-tile bucket histograms.
-     * Pass 1 counts per bucket with fire-and-forget LDS adds; pass 2 claims
-     * each row's offset at write time — no per-row offset state lives in
-     * registers, so tiles can be large and the loops unroll freely. */
+    constexpr int R = (PACKED ? kPartTileMax : kPartTileMin) / kPartThreads;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
 
-    uint64_t* rscratch = (uint64_t*)smem;         /* reorder mode: tile records */
-    unsigned* hist = (unsigned*)(smem + (pp.reorder ? (size_t)pp.tile_rows * 8 : 0));
-    unsigned* gbase = hist + kNB;
-    unsigned* nhist = gbase + kNB;                /* reorder mode: off[] prefix */
-    unsigned* ngbase = nhist + kNB;               /* reorder mode: claim counters */
-    unsigned* ovf = ngbase + kNB;                 /* [0] guard flag, [1] tile total, [2..5] scan */
-    uint64_t* klds = (uint64_t*)(ovf + 8);        /* staged key words */
+    uint64_t* scratch8 = (uint64_t*)smem;         /* the tile's records, bucket-major */
+    ulonglong2* scratch16 = (ulonglong2*)smem;
+    unsigned* hist = (unsigned*)(smem + kPartScratchBytes);  /* counts, then off[] */
+    unsigned* delta = hist + kNB;                 /* run base - off[] (mod 2^32) */
+    unsigned* nhist = delta + kNB;                /* null stream: counts, then bases */
+    unsigned* misc = nhist + kNB;                 /* [0] guard flag, [1] tile total, [2..] wave sums */
 
     const bool has_filter = pp.filter_idx >= 0;
     const bool has_val = pp.val_idx >= 0;
@@ -1997,19 +2018,16 @@ k_scan_partition(PartParams pp, const DevSeg* segs, const SegEx* segex,
      * record regions (cross-XCD partial-line sharing measured 3.7x write
      * amplification) */
     const int sub = blockIdx.x & 7;
-    if (pp.wg_streams) {
-        /* ngbase doubles as the per-bucket running base of this WG's own
-         * region — persistent across tiles */
-        for (int i = tid; i < kNB; i += 256) ngbase[i] = 0;
-        __syncthreads();
-    }
+    const uint64_t recmask = (pp.bits_k >= 64) ? ~0ULL : ((1ULL << pp.bits_k) - 1);
+    uint64_t* recs8 = (uint64_t*)recs;
 
     for (int tile = blockIdx.x; tile < pp.ntiles; tile += gridDim.x) {
         const int seg_idx = tile / pp.tiles_per_seg;
         const int tile_in_seg = tile % pp.tiles_per_seg;
         const int64_t t0 = (int64_t)tile_in_seg * pp.tile_rows;
         const int32_t seg_rows = segs[cols[1].seg_off + seg_idx].row_count;
-        int64_t t1 = t0 + pp.tile_rows;
+        if (t0 >= seg_rows) continue;   /* a tile past a short segment's end */
+        int64_t t1 = t0 + pp.tile_rows;   /* <= R rows per thread */
         if (t1 > seg_rows) t1 = seg_rows;
 
         const uint64_t* fwords = nullptr;
@@ -2026,7 +2044,6 @@ k_scan_partition(PartParams pp, const DevSeg* segs, const SegEx* segex,
             if (pp.has_filter_nulls)
                 fbm = (const uint8_t*)sg.blob + e.off_bitmap_bytes;
         }
-        /* the key column is decoded in BOTH passes — stage it in LDS */
         const DevSeg& sgk = segs[cols[1].seg_off + seg_idx];
         const SegEx& ek = segex[cols[1].seg_off + seg_idx];
         const uint32_t kwd = ek.w_values;
@@ -2035,18 +2052,6 @@ k_scan_partition(PartParams pp, const DevSeg* segs, const SegEx* segex,
         const uint8_t* kbm = pp.has_key_nulls
             ? (const uint8_t*)sgk.blob + ek.off_bitmap_bytes : nullptr;
         const uint64_t* kwords = sgk.blob + ek.off_values_words;
-        const int64_t kW0 = ((uint64_t)t0 * kwd) >> 6;
-        if (!pp.reorder && pp.wg_streams != 2) {
-            /* reorder mode reads keys straight from global both passes —
-             * the per-tile key window is L2-resident on the re-read, and
-             * the freed LDS buys the record scratch at 2 WGs/CU */
-            int64_t kW1 = kwd ? ((((uint64_t)t1 * kwd) + 63) >> 6) : 0;
-            int64_t nwords = (kwd == 0) ? 0 : (kW1 - kW0 + 1);
-            int64_t vec_words = (kwd == 0) ? 0 : (((uint64_t)seg_rows * kwd + 63) >> 6);
-            int64_t avail = vec_words - kW0;
-            if (nwords > avail) nwords = avail;
-            stage_copy(klds, sgk.blob + ek.off_values_words + kW0, nwords, tid);
-        }
         const uint64_t* vwords = nullptr;
         const uint8_t* vbm = nullptr;
         uint32_t vwd = 0;
@@ -2062,257 +2067,163 @@ k_scan_partition(PartParams pp, const DevSeg* segs, const SegEx* segex,
                 vbm = (const uint8_t*)sg.blob + e.off_bitmap_bytes;
         }
 
-        for (int i = tid; i < kNB; i += 256) { hist[i] = 0; nhist[i] = 0; }
-        if (tid == 0) ovf[0] = 0;
+        for (int i = tid; i < kNB; i += kPartThreads) { hist[i] = 0; nhist[i] = 0; }
+        if (tid == 0) misc[0] = 0;
         __syncthreads();
 
-        const int R = (pp.tile_rows + 255) / 256;
-        const bool single_pass = pp.wg_streams == 2;   /* claims straight off
-            the per-WG running bases: no count pass, no reserve */
-        /* pass 1: COUNT per bucket (no returns, no per-row state) */
-        if (pp.store_mode != 6 && !single_pass)
-        #pragma unroll 8
+        /* decode once: no atomics in this loop, so the unrolled rows' loads
+         * issue together. A row past the tile or segment end re-reads the
+         * last row and is marked invalid (with the small tile of packed
+         * records that is half of a thread's rows: small inputs only).
+         * Side rows keep the decoded value in rx. */
+        uint64_t rx[R];
+        uint64_t ry[PACKED ? 1 : R];
+        unsigned rb[R];
+        #pragma unroll
         for (int i = 0; i < R; i++) {
-            int64_t j = t0 + (int64_t)i * 256 + tid;
-            if (j >= t1) continue;
+            const int64_t j = t0 + (int64_t)i * kPartThreads + tid;
+            const int64_t jj = j < t1 ? j : t1 - 1;
+            bool keep = j < t1;
             if (has_filter) {
-                if (fbm && bm_get(fbm, j)) continue;
-                int64_t v = zz_dec(fmin + bp_gl(fwords, fmask, fwd, j));
-                if (v < pp.filter_lo || v > pp.filter_hi) continue;
+                int64_t f = zz_dec(fmin + bp_gl(fwords, fmask, fwd, jj));
+                keep = keep && f >= pp.filter_lo && f <= pp.filter_hi;
+                if (fbm) keep = keep && !bm_get(fbm, jj);
             }
-            int key_null = kbm && bm_get(kbm, j);
-            if (key_null) continue;              /* side rows counted in pass 2 */
-            uint64_t kraw = pp.reorder ? bp_gl(kwords, kmask, kwd, j)
-                                       : (bp_get_win(klds, kwd, j, kW0) & kmask);
-            uint64_t kzzfull = kmin + kraw;
-            if (kzzfull == ~0ULL) continue;      /* zz(INT64_MIN) = kEmptyKey */
-            unsigned b = pp.direct_mode
-                ? (unsigned)((kzzfull - pp.gmin_k) >> pp.dshift)
-                : (unsigned)(mix64((uint64_t)zz_dec(kzzfull)) >> 40) & (kNB - 1);
-            if (pp.store_mode == 7) { asm volatile("" :: "v"(b)); continue; }
-            if (has_val && vbm && bm_get(vbm, j)) atomicAdd(&nhist[b], 1u);
-            else atomicAdd(&hist[b], 1u);
+            const uint64_t kzz = kmin + bp_gl(kwords, kmask, kwd, jj);
+            const bool key_null = kbm && bm_get(kbm, jj);
+            uint64_t vzz = 0;
+            bool val_null = true;
+            if (has_val) {
+                vzz = vmin + bp_gl(vwords, vmask, vwd, jj);
+                val_null = vbm && bm_get(vbm, jj);
+            }
+            const uint64_t key = (uint64_t)zz_dec(kzz);
+            const unsigned b = pp.direct_mode
+                ? (unsigned)((kzz - pp.gmin_k) >> pp.dshift)
+                : (unsigned)(mix64(key) >> 40) & (kNB - 1);
+            unsigned cls;
+            uint64_t x, y = 0;
+            if (key_null || key == kEmptyKey) {
+                cls = kRowSide | (key_null ? 1u : 0u) | (val_null ? 2u : 0u);
+                x = (uint64_t)zz_dec(vzz);
+            } else if (has_val && val_null) {
+                cls = kRowNullVal | b;
+                x = key;
+            } else if constexpr (PACKED) {
+                cls = b;
+                x = kzz - pp.gmin_k;
+                if (has_val) x |= (vzz - pp.gmin_v) << pp.bits_k;
+            } else {
+                cls = b;
+                x = key;
+                y = has_val ? (uint64_t)zz_dec(vzz) : 0;
+            }
+            rb[i] = keep ? cls : kRowInvalid;
+            rx[i] = x;
+            if constexpr (!PACKED) ry[i] = y;
         }
-        __syncthreads();
-        /* reserve global space per bucket-sub (1 atomic per bucket/tile),
-         * then reuse hist/nhist as the pass-2 claim counters. Aligned mode
-         * reserves whole 8-record groups so no HBM line is split between
-         * two reservations (pad fill below). */
-        if (single_pass) {
-            /* no reserve: pass 2 claims ngbase[b]++ per record */
-        } else if (pp.wg_streams) {
-            /* local append into this WG's own region: no global atomics */
-            for (int i = tid; i < kNB; i += 256) {
-                unsigned c = hist[i];
-                if (c) {
-                    unsigned base = ngbase[i];
-                    if ((int64_t)(base + c) > pp.bucket_stride) { th->overflow = 1; ovf[0] = 1; base = 0; }
-                    gbase[i] = base;
-                    ngbase[i] = base + c;
-                    hist[i] = 0;
+        /* rank each row in its bucket; side rows (null key, INT64_MIN key)
+         * update their slots here and drop out */
+        #pragma unroll
+        for (int i = 0; i < R; i++) {
+            const unsigned c = rb[i];
+            if (c == kRowInvalid) continue;
+            if (c & kRowSide) {
+                const int side = c & 1;
+                th->side_used[side] = 1;
+                atomicAdd((unsigned long long*)&th->side_cnt[side], 1ULL);
+                if (pp.sum_slot >= 0 && !(c & 2)) {
+                    atomicAdd((unsigned long long*)&th->side_agg[side][2 * pp.sum_slot], rx[i]);
+                    atomicAdd((unsigned long long*)&th->side_agg[side][2 * pp.sum_slot + 1], 1ULL);
                 }
+                rb[i] = kRowInvalid;
+                continue;
             }
-        } else {
-        for (int i = tid; i < kNB; i += 256) {
-            unsigned c = hist[i];
-            if (c) {
-                unsigned res = pp.aligned ? ((c + 7u) & ~7u) : c;
-                unsigned long long base = atomicAdd(&cursors[i * 8 + sub], (unsigned long long)res);
-                if ((int64_t)(base + res) > pp.bucket_stride) { th->overflow = 1; ovf[0] = 1; base = 0; }
-                gbase[i] = (unsigned)base;
-                if (!pp.reorder) hist[i] = 0;   /* reorder keeps counts for off[]/pads */
-            }
-            unsigned nc = nhist[i];
-            if (nc) {
-                unsigned res = pp.aligned ? ((nc + 7u) & ~7u) : nc;
-                unsigned long long base = atomicAdd(&ncursors[i * 8 + sub], (unsigned long long)res);
-                if ((int64_t)(base + res) > pp.nbucket_stride) { th->overflow = 1; ovf[0] = 1; base = 0; }
-                ngbase[i] = (unsigned)base;
-                nhist[i] = 0;
-            }
-        }
+            const unsigned b = c & (kNB - 1);
+            const unsigned rank = atomicAdd((c & kRowNullVal) ? &nhist[b] : &hist[b], 1u);
+            rb[i] = c | (rank << 10);
         }
         __syncthreads();
-        if (pp.reorder) {
-            /* exclusive prefix of hist -> nhist (off[]), zero claim counters;
-             * 256 threads x 4 consecutive buckets, wave scan + 4 wave sums */
-            const int lane_ = tid & 63, wave_ = tid >> 6;
-            const int b0 = tid * 4;
-            unsigned c0 = hist[b0], c1 = hist[b0 + 1], c2 = hist[b0 + 2], c3 = hist[b0 + 3];
-            unsigned local = c0 + c1 + c2 + c3;
+
+        /* exclusive block scan of hist -> off[] (two consecutive buckets per
+         * thread, wave scan + wave sums), and one reservation per non-empty
+         * bucket in this workgroup's (bucket, sub) region */
+        {
+            const int lane = tid & 63, wave = tid >> 6;
+            constexpr int BPT = kNB / kPartThreads;   /* consecutive buckets per thread */
+            const int b0 = tid * BPT;
+            unsigned cnt[BPT];
+            unsigned local = 0;
+            #pragma unroll
+            for (int h = 0; h < BPT; h++) { cnt[h] = hist[b0 + h]; local += cnt[h]; }
             unsigned pre = local;
             for (int sh = 1; sh < 64; sh <<= 1) {
                 unsigned o = (unsigned)__shfl_up((int)pre, sh, 64);
-                if (lane_ >= sh) pre += o;
+                if (lane >= sh) pre += o;
             }
-            if (lane_ == 63) ovf[2 + wave_] = pre;
+            if (lane == 63) misc[2 + wave] = pre;
             __syncthreads();
-            unsigned woff = 0;
-            for (int w2 = 0; w2 < wave_; w2++) woff += ovf[2 + w2];
-            unsigned excl = woff + pre - local;
-            nhist[b0] = excl;
-            nhist[b0 + 1] = excl + c0;
-            nhist[b0 + 2] = excl + c0 + c1;
-            nhist[b0 + 3] = excl + c0 + c1 + c2;
-            ngbase[b0] = 0; ngbase[b0 + 1] = 0; ngbase[b0 + 2] = 0; ngbase[b0 + 3] = 0;
-            if (tid == 255) ovf[1] = excl + local;
-            __syncthreads();
+            unsigned off = pre - local;
+            for (int w2 = 0; w2 < wave; w2++) off += misc[2 + w2];
+            if (tid == kPartThreads - 1) misc[1] = off + local;
+            #pragma unroll
+            for (int h = 0; h < BPT; off += cnt[h], h++) {
+                const int b = b0 + h;
+                const unsigned c = cnt[h];
+                if (c) {
+                    unsigned long long base = atomicAdd(&cursors[b * 8 + sub], (unsigned long long)c);
+                    if ((int64_t)(base + c) > pp.bucket_stride) { th->overflow = 1; misc[0] = 1; base = 0; }
+                    delta[b] = (unsigned)base - off;
+                }
+                hist[b] = off;
+                const unsigned nc = nhist[b];
+                if (nc) {
+                    unsigned long long base = atomicAdd(&ncursors[b * 8 + sub], (unsigned long long)nc);
+                    if ((int64_t)(base + nc) > pp.nbucket_stride) { th->overflow = 1; misc[0] = 1; base = 0; }
+                    nhist[b] = (unsigned)base;
+                }
+            }
         }
-        uint64_t* recs8 = (uint64_t*)recs;
-        if (ovf[0] != 1) {   /* LDS flag: uniform across the block */
-            /* pass 2: claim offset, decode, write */
-            if (pp.store_mode < 3)
-            #pragma unroll 8
+        __syncthreads();
+
+        if (misc[0] != 1) {   /* LDS flag: uniform across the block */
+            #pragma unroll
             for (int i = 0; i < R; i++) {
-                int64_t j = t0 + (int64_t)i * 256 + tid;
-                if (j >= t1) continue;
-                if (has_filter) {
-                    if (fbm && bm_get(fbm, j)) continue;
-                    int64_t v = zz_dec(fmin + bp_gl(fwords, fmask, fwd, j));
-                    if (v < pp.filter_lo || v > pp.filter_hi) continue;
-                }
-                int key_null = kbm && bm_get(kbm, j);
-                uint64_t kzzfull = 0;
-                uint64_t key = 0;
-                if (!key_null) {
-                    kzzfull = kmin + ((pp.reorder || pp.wg_streams == 2)
-                        ? bp_gl(kwords, kmask, kwd, j)
-                        : (bp_get_win(klds, kwd, j, kW0) & kmask));
-                    key = (uint64_t)zz_dec(kzzfull);
-                }
-                int val_null = has_val ? (vbm && bm_get(vbm, j)) : 1;
-
-                if (key_null || key == kEmptyKey) {
-                    int side = key_null ? 1 : 0;
-                    th->side_used[side] = 1;
-                    atomicAdd((unsigned long long*)&th->side_cnt[side], 1ULL);
-                    if (pp.sum_slot >= 0 && !val_null) {
-                        uint64_t val = (uint64_t)zz_dec(vmin + bp_gl(vwords, vmask, vwd, j));
-                        atomicAdd((unsigned long long*)&th->side_agg[side][2 * pp.sum_slot], val);
-                        atomicAdd((unsigned long long*)&th->side_agg[side][2 * pp.sum_slot + 1], 1ULL);
-                    }
-                    continue;
-                }
-
-                unsigned b = pp.direct_mode
-                    ? (unsigned)((kzzfull - pp.gmin_k) >> pp.dshift)
-                    : (unsigned)(mix64(key) >> 40) & (kNB - 1);
-                int64_t sb = pp.wg_streams
-                    ? (int64_t)b * gridDim.x + blockIdx.x
-                    : (int64_t)b * 8 + sub;
-                if (has_val && val_null) {
-                    unsigned off = atomicAdd(&nhist[b], 1u);
-                    nrecs[sb * pp.nbucket_stride + ngbase[b] + off] = key;
-                } else if (pp.reorder) {
-                    uint64_t rec = kzzfull - pp.gmin_k;
-                    if (has_val) {
-                        uint64_t vzz = (vmin + bp_gl(vwords, vmask, vwd, j)) - pp.gmin_v;
-                        rec |= vzz << pp.bits_k;
-                    }
-                    unsigned off = atomicAdd(&ngbase[b], 1u);
-                    rscratch[nhist[b] + off] = rec;
-                } else if (pp.packed_mode) {
-                    unsigned off;
-                    unsigned base;
-                    if (single_pass) {
-                        off = atomicAdd(&ngbase[b], 1u);
-                        base = 0;
-                        if ((int64_t)off >= pp.bucket_stride) {
-                            th->overflow = 1;
-                            continue;
-                        }
-                    } else {
-                        off = atomicAdd(&hist[b], 1u);
-                        base = gbase[b];
-                    }
-                    uint64_t rec = kzzfull - pp.gmin_k;
-                    if (has_val) {
-                        uint64_t vzz = (vmin + bp_gl(vwords, vmask, vwd, j)) - pp.gmin_v;
-                        rec |= vzz << pp.bits_k;
-                    }
-                    uint64_t* dst = &recs8[sb * pp.bucket_stride + base + off];
-                    if (pp.store_mode == 1) {
-                        /* write-through (sc1): drops the line from L2 — no
-                         * partial-line RMW fill on eviction */
-                        __hip_atomic_store((unsigned long long*)dst, rec,
-                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    } else if (pp.store_mode == 2) {
-                        /* timing-floor probe: keep rec alive, skip the store */
-                        asm volatile("" :: "v"(rec));
-                    } else {
-                        *dst = rec;
-                    }
+                const unsigned c = rb[i];
+                if (c == kRowInvalid) continue;
+                const unsigned b = c & (kNB - 1);
+                const unsigned rank = (c >> 10) & 0x3FFFu;
+                if (c & kRowNullVal) {
+                    nrecs[((int64_t)b * 8 + sub) * pp.nbucket_stride + nhist[b] + rank] = rx[i];
+                } else if constexpr (PACKED) {
+                    scratch8[hist[b] + rank] = rx[i];
                 } else {
-                    unsigned off = atomicAdd(&hist[b], 1u);
-                    uint64_t val = 0;
-                    if (has_val) {
-                        val = (uint64_t)zz_dec(vmin + bp_gl(vwords, vmask, vwd, j));
-                    }
-                    recs[sb * pp.bucket_stride + gbase[b] + off] =
-                        make_ulonglong2(key, val);
+                    scratch16[hist[b] + rank] = make_ulonglong2(rx[i], ry[i]);
                 }
             }
-            if (pp.reorder) {
-                /* stream the bucket-major tile to the aligned global claims,
-                 * pads fused in: one wave owns each bucket run, lanes write
-                 * adjacent records, every 64B line is covered by exactly one
-                 * wave store instruction — no partial lines, no separate pad
-                 * pass re-dirtying lines */
-                __syncthreads();
-                const int lane_ = tid & 63, wave_ = tid >> 6;
-                for (int b = wave_; b < kNB; b += 4) {
-                    unsigned c = hist[b];
-                    if (!c) continue;
-                    unsigned cp = (c + 7u) & ~7u;
-                    const unsigned offb = nhist[b];
-                    uint64_t* dst = recs8 + ((int64_t)b * 8 + sub) * pp.bucket_stride
-                                  + gbase[b];
-                    for (unsigned r = lane_; r < cp; r += 64) {
-                        dst[r] = (r < c) ? rscratch[offb + r]
-                                         : 0x8000000000000000ULL;
-                    }
-                }
-            }
-            /* pad the tail of every claim group up to the 8-record boundary
-             * (same lines the real records ended on — completes them) */
-            if (pp.aligned && !pp.reorder) {
-                __syncthreads();
-                for (int b = tid; b < kNB; b += 256) {
-                    unsigned c = hist[b];
-                    if (c & 7u) {
-                        int64_t sb = (int64_t)b * 8 + sub;
-                        unsigned pad = 8u - (c & 7u);
-                        if (pp.packed_mode) {
-                            for (unsigned p = 0; p < pad; p++)
-                                recs8[sb * pp.bucket_stride + gbase[b] + c + p] =
-                                    0x8000000000000000ULL;
-                        } else {
-                            for (unsigned p = 0; p < pad; p++)
-                                recs[sb * pp.bucket_stride + gbase[b] + c + p] =
-                                    make_ulonglong2(kEmptyKey, 0);
-                        }
-                    }
-                    /* null-value stream pads (absent in reorder mode, where
-                     * nhist holds the off[] prefix and nrecs is null) */
-                    unsigned nc = (nrecs && !pp.reorder) ? nhist[b] : 0;
-                    if (nc & 7u) {
-                        int64_t sb = (int64_t)b * 8 + sub;
-                        unsigned pad = 8u - (nc & 7u);
-                        for (unsigned p = 0; p < pad; p++)
-                            nrecs[sb * pp.nbucket_stride + ngbase[b] + nc + p] =
-                                kEmptyKey;
-                    }
+            __syncthreads();
+            const unsigned total = misc[1];
+            for (unsigned r = tid; r < total; r += kPartThreads) {
+                if constexpr (PACKED) {
+                    const uint64_t rec = scratch8[r];
+                    const uint64_t krel = rec & recmask;
+                    const unsigned b = pp.direct_mode
+                        ? (unsigned)(krel >> pp.dshift)
+                        : (unsigned)(mix64((uint64_t)zz_dec(pp.gmin_k + krel)) >> 40) & (kNB - 1);
+                    recs8[((int64_t)b * 8 + sub) * pp.bucket_stride + (unsigned)(delta[b] + r)] = rec;
+                } else {
+                    const ulonglong2 rec = scratch16[r];
+                    const unsigned b = pp.direct_mode
+                        ? (unsigned)((zz_enc64((int64_t)rec.x) - pp.gmin_k) >> pp.dshift)
+                        : (unsigned)(mix64(rec.x) >> 40) & (kNB - 1);
+                    recs[((int64_t)b * 8 + sub) * pp.bucket_stride + (unsigned)(delta[b] + r)] = rec;
                 }
             }
         }
         __syncthreads();
     }
-    if (pp.wg_streams) {
-        /* publish this WG's final per-bucket counts */
-        for (int i = tid; i < kNB; i += 256)
-            cursors[(int64_t)i * gridDim.x + blockIdx.x] = ngbase[i];
-    }
 }
+
 
 
 /* Phase B: one workgroup per bucket. LDS table slot = {key, cnt|nonnull<<32
@@ -2326,7 +2237,7 @@ k_bucket_agg(const ulonglong2* recs, const unsigned long long* cursors,
              OutGroup* out, unsigned long long* out_counter, int64_t out_cap,
              TableHdr* th, int sum_slot, int agg_count,
              int packed_mode, int bits_k, uint64_t gmin_k, uint64_t gmin_v,
-             int aligned, int nsub)
+             int nsub)
 {
     __shared__ unsigned long long tab[kHSlots * 3];
     const int tid = threadIdx.x;
@@ -2355,19 +2266,14 @@ k_bucket_agg(const ulonglong2* recs, const unsigned long long* cursors,
     const uint64_t* rows8 = (const uint64_t*)recs + ((int64_t)bucket * nsub + sub) * bucket_stride;
     /* 4 records per thread per pass: independent probes overlap LDS latency */
     int64_t i = tid;
-    /* pads (aligned claims): packed = bit 63, 16B = key == kEmptyKey —
-     * both map kv.x to kEmptyKey, which PROBE skips (real INT64_MIN keys
-     * are side-slotted in phase A and never enter the streams) */
+    /* real INT64_MIN keys are side-slotted in phase A and never enter the
+     * streams, so kEmptyKey is free to mark an empty table slot */
     #define LOADKV(kv, idx)                                                  \
         ulonglong2 kv;                                                       \
         if (packed_mode) {                                                   \
             uint64_t r_ = rows8[idx];                                        \
-            if (aligned && (int64_t)r_ < 0) {                                \
-                kv.x = kEmptyKey; kv.y = 0;                                  \
-            } else {                                                         \
-                kv.x = (uint64_t)zz_dec(gmin_k + (r_ & kmask));              \
-                kv.y = (uint64_t)zz_dec(gmin_v + (r_ >> bits_k));            \
-            }                                                                \
+            kv.x = (uint64_t)zz_dec(gmin_k + (r_ & kmask));                  \
+            kv.y = (uint64_t)zz_dec(gmin_v + (r_ >> bits_k));                \
         } else {                                                             \
             kv = rows[idx];                                                  \
         }
@@ -2434,7 +2340,6 @@ k_bucket_agg(const ulonglong2* recs, const unsigned long long* cursors,
         const uint64_t* nrows = nrecs + ((int64_t)bucket * 8 + sub) * nbucket_stride;
         for (int64_t i = tid; i < nn && !full; i += 256) {
             uint64_t key = nrows[i];
-            if (key == kEmptyKey) continue;      /* aligned-claim pad */
             uint64_t s = mix64(key) & (kHSlots - 1);
             int found = 0;
             for (int it = 0; it < kHSlots; it++) {
@@ -2486,11 +2391,6 @@ k_bucket_agg(const ulonglong2* recs, const unsigned long long* cursors,
  * no probe loop, no CAS, no stored keys. Slot = {cnt|nonnull<<32, sum}.
  * Semantics identical to k_bucket_agg (registry.cpp:1783-1834 insert +
  * udf/sum.c null-propagating sum); only the table organisation differs. */
-__device__ __forceinline__ uint64_t zz_enc64(int64_t v)
-{
-    return ((uint64_t)v << 1) ^ (uint64_t)(v >> 63);
-}
-
 __global__ void __launch_bounds__(256)
 k_bucket_agg_direct(const ulonglong2* recs, const unsigned long long* cursors,
                     int64_t bucket_stride,
@@ -2530,6 +2430,10 @@ k_bucket_agg_direct(const ulonglong2* recs, const unsigned long long* cursors,
         const ulonglong2* rows = recs + ((int64_t)bucket * nsub + sub) * bucket_stride;
         const uint64_t* rows8 = (const uint64_t*)recs + ((int64_t)bucket * nsub + sub) * bucket_stride;
         int64_t i = tid;
+        /* a packed record with bit 63 set, or a 16-byte one with key
+         * kEmptyKey, is skipped: phase A stores neither (direct mode is only
+         * chosen with bit 63 spare, INT64_MIN keys are side-slotted), so the
+         * skips are never taken */
         #define DACCR(r_)                                                    \
             {                                                                \
                 uint64_t k_ = ((int64_t)(r_) < 0 && packed_mode)             \
@@ -2586,7 +2490,7 @@ k_bucket_agg_direct(const ulonglong2* recs, const unsigned long long* cursors,
             const uint64_t* nrows = nrecs + ((int64_t)bucket * 8 + sub) * nbucket_stride;
             for (int64_t i = tid; i < nn; i += 256) {
                 uint64_t key = nrows[i];
-                if (key == kEmptyKey) continue;         /* pad */
+                if (key == kEmptyKey) continue;         /* never stored: side-slotted */
                 uint64_t idx = (zz_enc64((int64_t)key) - gmin_k) - base_rel;
                 atomicAdd(&cntnn[idx], 1ULL);           /* cnt only: null value */
             }
@@ -4247,11 +4151,32 @@ hipError_t ytql_launch_scan_partition(const PartParams* pp, const DevSeg* segs,
                                       TableHdr* th,
                                       unsigned long long* cursors, void* recs,
                                       unsigned long long* ncursors, uint64_t* nrecs,
-                                      size_t lds_bytes, int grid, hipStream_t st)
+                                      int grid, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_scan_partition, dim3(grid), dim3(256), lds_bytes, st,
-                       *pp, segs, segex, cols, th, cursors, (ulonglong2*)recs,
-                       ncursors, nrecs);
+    /* 64 KiB record scratch + histograms: above the 64 KiB a launch may
+     * request by default, so raise the kernel's limit first, once per
+     * device and instantiation */
+    static std::atomic<bool> raised[2][64];
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const int inst = pp->packed_mode ? 1 : 0;
+    if (dev < 0 || dev >= 64 || !raised[inst][dev].load(std::memory_order_acquire)) {
+        const void* fn = inst ? (const void*)k_scan_partition<true>
+                              : (const void*)k_scan_partition<false>;
+        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)kPartLdsBytes);
+        if (e != hipSuccess) return e;
+        if (dev >= 0 && dev < 64) raised[inst][dev].store(true, std::memory_order_release);
+    }
+    if (pp->packed_mode)
+        hipLaunchKernelGGL(k_scan_partition<true>, dim3(grid), dim3(kPartThreads),
+                           kPartLdsBytes, st, *pp, segs, segex, cols, th, cursors,
+                           (ulonglong2*)recs, ncursors, nrecs);
+    else
+        hipLaunchKernelGGL(k_scan_partition<false>, dim3(grid), dim3(kPartThreads),
+                           kPartLdsBytes, st, *pp, segs, segex, cols, th, cursors,
+                           (ulonglong2*)recs, ncursors, nrecs);
     return hipGetLastError();
 }
 
@@ -4264,13 +4189,13 @@ hipError_t ytql_launch_bucket_agg(const void* recs, const unsigned long long* cu
                                   TableHdr* th, int sum_slot, int agg_count,
                                   int packed_mode, int bits_k,
                                   uint64_t gmin_k, uint64_t gmin_v,
-                                  int aligned, int nsub, hipStream_t st)
+                                  int nsub, hipStream_t st)
 {
     hipLaunchKernelGGL(k_bucket_agg, dim3(kNB), dim3(256), 0, st,
                        (const ulonglong2*)recs, cursors, bucket_stride,
                        nrecs, ncursors, nbucket_stride,
                        out, out_counter, out_cap, th, sum_slot, agg_count,
-                       packed_mode, bits_k, gmin_k, gmin_v, aligned, nsub);
+                       packed_mode, bits_k, gmin_k, gmin_v, nsub);
     return hipGetLastError();
 }
 
