@@ -75,6 +75,17 @@ constexpr int kMaxCols = 8;
 constexpr int kMaxAggs = 4;
 constexpr int kMaxStrPreds = 4;    /* string predicates with a bitmap per filter */
 
+/* The scalar words of the chunk setup (k_parse_segments, k_scan_nullflags,
+ * the kernels' error word) in one block: one H2D copy of a host image sets
+ * them, one D2H copy brings them back. */
+struct SetupWords {
+    unsigned col_null[kMaxCols];          /* bit0 nulls seen, bit1 unknown */
+    unsigned maxw;                        /* widest value vector */
+    unsigned err[3];                      /* [0] kernel error, [1] join dups */
+    unsigned long long zzmin[kMaxCols];   /* image: ~0 */
+    unsigned long long zzmax[kMaxCols];   /* image: 0 */
+};
+
 /* One compiled plan for the device: programs are concatenated postfix
  * streams with (offset,len) per role. */
 constexpr int kMaxProj = 8;
@@ -221,6 +232,19 @@ struct OutGroup {
     uint64_t agg_bits[kMaxAggs];
     uint64_t agg_nonnull[kMaxAggs];
 };
+
+/* Compacted output record of the partitioned path when the whole query runs
+ * in one call (yt_gpu_query_execute): that family has one int64 key, at most
+ * one sum and an optional sum(1), and its null key is a side slot, so 32 of
+ * OutGroup's 88 bytes say everything. The D2H of the groups is the largest
+ * copy of the step. */
+struct SlimGroup {
+    uint64_t key_bits;
+    uint64_t cnt;
+    uint64_t sum_bits;        /* the one sum; 0 without */
+    uint64_t sum_nonnull;
+};
+static_assert(sizeof(SlimGroup) == 32, "two 16-byte stores per group");
 
 /* Fast-shape descriptor (analysed by the host):
  * filter: optional int64 range on one column; key: direct column or none;

@@ -38,12 +38,12 @@ hipError_t ytql_launch_scan_partition(const PartParams*, const DevSeg*, const Se
                                       int, hipStream_t);
 hipError_t ytql_launch_bucket_agg(const void*, const unsigned long long*, int64_t,
                                   const uint64_t*, const unsigned long long*, int64_t,
-                                  OutGroup*, unsigned long long*, int64_t,
+                                  OutGroup*, unsigned long long*, int64_t, int,
                                   TableHdr*, int, int, int, int,
                                   uint64_t, uint64_t, int, hipStream_t);
 hipError_t ytql_launch_bucket_agg_direct(const void*, const unsigned long long*, int64_t,
                                          const uint64_t*, const unsigned long long*, int64_t,
-                                         OutGroup*, unsigned long long*, int64_t,
+                                         OutGroup*, unsigned long long*, int64_t, int,
                                          TableHdr*, int, int, int, int,
                                          uint64_t, uint64_t, int, int, hipStream_t);
 hipError_t ytql_launch_topk_hist(const DevPlan*, const DevSeg*, const SegEx*,
@@ -1082,6 +1082,9 @@ struct DeviceRun {
     SegEx* d_segex = nullptr;
     int32_t* d_off = nullptr;
     int32_t* d_cnt = nullptr;
+    /* d_maxw, d_err, d_colnull and d_zzrange point into d_setup */
+    SetupWords* d_setup = nullptr;
+    SetupWords* h_setup = nullptr;     /* pinned: the image, then the readback */
     unsigned* d_maxw = nullptr;
     unsigned* d_err = nullptr;
     TableHdr* d_th = nullptr;
@@ -1100,6 +1103,14 @@ struct DeviceRun {
     int nsegs = 0;
     int64_t groups_capacity = 0;
     bool groups_compacted = false;     /* d_groups already holds final groups */
+    /* set by yt_gpu_query_execute alone: the partitioned path may leave
+     * SlimGroups in d_groups. groups_slim says that it did. */
+    bool want_slim = false;
+    bool groups_slim = false;
+    /* the table header as run_partitioned last read it (pinned); valid
+     * while th_valid, so the caller need not fetch it again */
+    TableHdr* h_th = nullptr;
+    bool th_valid = false;
     unsigned col_null_flags[kMaxCols] = {0};
     uint64_t col_zzmin[kMaxCols] = {0};
     uint64_t col_zzmax[kMaxCols] = {0};
@@ -1111,20 +1122,19 @@ struct DeviceRun {
         g_pool.put(d_segex);
         g_pool.put(d_off);
         g_pool.put(d_cnt);
-        g_pool.put(d_maxw);
-        g_pool.put(d_err);
+        g_pool.put(d_setup);
+        g_pool.put(h_setup);
         g_pool.put(d_th);
         g_pool.put(d_slots);
         g_pool.put(d_groups);
         g_pool.put(d_counter);
         g_pool.put(d_gaccum);
         g_pool.put(d_fastcols);
-        g_pool.put(d_colnull);
-        g_pool.put(d_zzrange);
         g_pool.put(d_cursors);
         g_pool.put(d_recs);
         g_pool.put(d_ncursors);
         g_pool.put(d_nrecs);
+        g_pool.put(h_th);
     }
 };
 
@@ -1210,38 +1220,40 @@ static int setup_chunk(const YtChunk* chunk, DeviceRun* R, unsigned* maxw_out,
     HIP_CHECK(pool_alloc(&R->d_segex, sizeof(SegEx) * R->nsegs));
     HIP_CHECK(pool_alloc(&R->d_off, sizeof(int32_t) * ncols));
     HIP_CHECK(pool_alloc(&R->d_cnt, sizeof(int32_t) * ncols));
-    HIP_CHECK(pool_alloc(&R->d_maxw, sizeof(unsigned)));
-    HIP_CHECK(pool_alloc(&R->d_err, sizeof(unsigned)));
-    HIP_CHECK(pool_alloc(&R->d_colnull, sizeof(unsigned) * kMaxCols));
-    HIP_CHECK(hipMemsetAsync(R->d_colnull, 0, sizeof(unsigned) * kMaxCols, R->stream));
-    HIP_CHECK(pool_alloc(&R->d_zzrange, sizeof(uint64_t) * 2 * kMaxCols));
-    HIP_CHECK(hipMemsetAsync(R->d_zzrange, 0xFF, sizeof(uint64_t) * kMaxCols, R->stream));
-    HIP_CHECK(hipMemsetAsync(R->d_zzrange + kMaxCols, 0, sizeof(uint64_t) * kMaxCols, R->stream));
+    /* the scalar words: one block, set by one copy of a pinned host image
+     * and read back into it by one copy (it was five fills and four copies
+     * into pageable memory) */
+    HIP_CHECK(pool_alloc(&R->d_setup, sizeof(SetupWords)));
+    HIP_CHECK(pool_alloc_host(&R->h_setup, sizeof(SetupWords)));
+    R->d_maxw = &R->d_setup->maxw;
+    R->d_err = R->d_setup->err;
+    R->d_colnull = R->d_setup->col_null;
+    R->d_zzrange = R->d_setup->zzmin;
+    static_assert(offsetof(SetupWords, zzmax) ==
+                  offsetof(SetupWords, zzmin) + sizeof(uint64_t) * kMaxCols,
+                  "d_zzrange: kMaxCols minima, then kMaxCols maxima");
+    memset(R->h_setup, 0, sizeof(SetupWords));
+    memset(R->h_setup->zzmin, 0xFF, sizeof(R->h_setup->zzmin));
+    HIP_CHECK(hipMemcpyAsync(R->d_setup, R->h_setup, sizeof(SetupWords),
+                             hipMemcpyHostToDevice, R->stream));
     HIP_CHECK(hipMemcpyAsync(R->d_segs, R->h_segs.data(), sizeof(DevSeg) * R->nsegs,
                              hipMemcpyHostToDevice, R->stream));
     HIP_CHECK(hipMemcpyAsync(R->d_off, R->h_off.data(), sizeof(int32_t) * ncols,
                              hipMemcpyHostToDevice, R->stream));
     HIP_CHECK(hipMemcpyAsync(R->d_cnt, R->h_cnt.data(), sizeof(int32_t) * ncols,
                              hipMemcpyHostToDevice, R->stream));
-    HIP_CHECK(hipMemsetAsync(R->d_maxw, 0, sizeof(unsigned), R->stream));
-    HIP_CHECK(hipMemsetAsync(R->d_err, 0, sizeof(unsigned), R->stream));
     HIP_CHECK(ytql_launch_parse_segments(R->d_segs, R->nsegs, R->d_segex, R->d_maxw,
                                          R->d_colnull, R->d_zzrange,
                                          R->d_zzrange + kMaxCols, R->stream));
     HIP_CHECK(ytql_launch_scan_nullflags(R->d_segs, R->d_segex, R->nsegs,
                                          R->d_colnull, R->stream));
-    HIP_CHECK(hipMemcpyAsync(maxw_out, R->d_maxw, sizeof(unsigned),
-                             hipMemcpyDeviceToHost, R->stream));
-    HIP_CHECK(hipMemcpyAsync(R->col_null_flags, R->d_colnull,
-                             sizeof(unsigned) * kMaxCols,
-                             hipMemcpyDeviceToHost, R->stream));
-    HIP_CHECK(hipMemcpyAsync(R->col_zzmin, R->d_zzrange,
-                             sizeof(uint64_t) * kMaxCols,
-                             hipMemcpyDeviceToHost, R->stream));
-    HIP_CHECK(hipMemcpyAsync(R->col_zzmax, R->d_zzrange + kMaxCols,
-                             sizeof(uint64_t) * kMaxCols,
+    HIP_CHECK(hipMemcpyAsync(R->h_setup, R->d_setup, sizeof(SetupWords),
                              hipMemcpyDeviceToHost, R->stream));
     HIP_CHECK(hipStreamSynchronize(R->stream));
+    *maxw_out = R->h_setup->maxw;
+    memcpy(R->col_null_flags, R->h_setup->col_null, sizeof(R->col_null_flags));
+    memcpy(R->col_zzmin, R->h_setup->zzmin, sizeof(R->col_zzmin));
+    memcpy(R->col_zzmax, R->h_setup->zzmax, sizeof(R->col_zzmax));
     return YT_OK;
 fail:
     return rc;
@@ -1557,7 +1569,11 @@ static int run_partitioned(const YtPlan* plan, const YtChunk* chunk,
         }
         if (cap_groups > rows + 16) cap_groups = rows + 16;
         R->groups_capacity = cap_groups;
-        HIP_CHECK(pool_alloc(&R->d_groups, sizeof(OutGroup) * cap_groups));
+        const int slim = R->want_slim ? 1 : 0;
+        HIP_CHECK(pool_alloc(&R->d_groups,
+                             (slim ? sizeof(SlimGroup) : sizeof(OutGroup)) * cap_groups));
+        if (!R->h_th) HIP_CHECK(pool_alloc_host(&R->h_th, sizeof(TableHdr)));
+        R->th_valid = false;
         HIP_CHECK(pool_alloc(&R->d_counter, sizeof(unsigned long long)));
         HIP_CHECK(hipMemsetAsync(R->d_counter, 0, sizeof(unsigned long long), R->stream));
 
@@ -1573,19 +1589,22 @@ static int run_partitioned(const YtPlan* plan, const YtChunk* chunk,
         if (pp.direct_mode) {
             HIP_CHECK(ytql_launch_bucket_agg_direct(R->d_recs, R->d_cursors, pp.bucket_stride,
                                              R->d_nrecs, R->d_ncursors, pp.nbucket_stride,
-                                             R->d_groups, R->d_counter, cap_groups,
+                                             R->d_groups, R->d_counter, cap_groups, slim,
                                              R->d_th, pp.sum_slot, pp.agg_count,
                                              pp.packed_mode, pp.bits_k,
                                              pp.gmin_k, pp.gmin_v, pp.dshift, nsub, R->stream));
         } else {
             HIP_CHECK(ytql_launch_bucket_agg(R->d_recs, R->d_cursors, pp.bucket_stride,
                                              R->d_nrecs, R->d_ncursors, pp.nbucket_stride,
-                                             R->d_groups, R->d_counter, cap_groups,
+                                             R->d_groups, R->d_counter, cap_groups, slim,
                                              R->d_th, pp.sum_slot, pp.agg_count,
                                              pp.packed_mode, pp.bits_k,
                                              pp.gmin_k, pp.gmin_v, nsub, R->stream));
         }
         HIP_CHECK(hipEventRecord(ev2, R->stream));
+        /* the header rides the synchronisation that the events need anyway */
+        HIP_CHECK(hipMemcpyAsync(R->h_th, R->d_th, sizeof(TableHdr),
+                                 hipMemcpyDeviceToHost, R->stream));
         HIP_CHECK(hipStreamSynchronize(R->stream));
         float msA = 0, msB = 0;
         HIP_CHECK(hipEventElapsedTime(&msA, ev0, ev1));
@@ -1596,9 +1615,7 @@ static int run_partitioned(const YtPlan* plan, const YtChunk* chunk,
             stats->kernel_other_ms += msB;
         }
         /* overflow==1 → capacity guard; retry on the direct path */
-        TableHdr th;
-        HIP_CHECK(hipMemcpy(&th, R->d_th, sizeof(th), hipMemcpyDeviceToHost));
-        if (th.overflow == 1) {
+        if (R->h_th->overflow == 1) {
             /* reset and fall back */
             g_pool.put(R->d_groups); R->d_groups = nullptr;
             g_pool.put(R->d_counter); R->d_counter = nullptr;
@@ -1616,6 +1633,8 @@ static int run_partitioned(const YtPlan* plan, const YtChunk* chunk,
             *done = false;
         } else {
             R->groups_compacted = true;
+            R->groups_slim = slim != 0;
+            R->th_valid = true;
             *done = true;
         }
     }
@@ -1863,13 +1882,28 @@ static void finalize_row(const YtPlan* plan, uint8_t key_type,
     *nrow = n;
 }
 
+/* SlimGroups on their way to the host: the copy was queued in `count` slices
+ * of `per` groups each (the last one shorter), with an event after every
+ * slice. A reader waits for the event of a slice before it touches it. */
+constexpr int kGroupSlices = 8;
+struct SlimSlices {
+    hipEvent_t ev[kGroupSlices];
+    int count;
+    int64_t per;
+};
+
+/* `groups` holds OutGroups, or, when `slim` is given, is null and `slim`
+ * holds the SlimGroups of the partitioned path; `slices` (slim only) is null
+ * when the records have already landed. */
 static int emit_rows(const YtPlan* plan, const YtChunk* chunk,
                      const DevPlan* dp,
                      const OutGroup* groups, int64_t ngroups,
                      const TableHdr& th, int has_any_row_global,
                      const uint64_t* gaccum, int used_fast_global,
                      int64_t output_row_limit, int* out_limited,
-                     YtRowset* output, char* errbuf, size_t errlen)
+                     YtRowset* output, char* errbuf, size_t errlen,
+                     const SlimGroup* slim = nullptr,
+                     const SlimSlices* slices = nullptr)
 {
     uint8_t col_types[kMaxCols];
     memset(col_types, YT_VT_INT64, sizeof(col_types));
@@ -1960,6 +1994,48 @@ static int emit_rows(const YtPlan* plan, const YtChunk* chunk,
         return rc_;
     };
 
+    /* a SlimGroup row. Without projections the family's values are written
+     * straight into the rowset: key, then per aggregate sum(1) = cnt or the
+     * one sum (NULL when no argument was non-null) — what finalize_row
+     * yields for them. Anything else goes the general way. */
+    bool slim_direct = slim && !plan->project_count && !kp && has_key;
+    for (int a = 0; a < plan->agg_count; a++) {
+        int f = plan->aggs[a]->func;
+        if (f != YT_AGG_SUM && f != YT_AGG_SUM1) slim_direct = false;
+    }
+    auto emit_slim_at = [&](YtValue* dst, const SlimGroup& g) -> int {
+        if (!slim_direct) {
+            uint64_t ab[kMaxAggs], an[kMaxAggs];
+            for (int a = 0; a < kMaxAggs; a++) {
+                ab[a] = g.sum_bits;
+                an[a] = g.sum_nonnull;
+            }
+            return emit_at(dst, g.key_bits, 0, g.cnt, ab, an);
+        }
+        dst[0].id = 0;
+        dst[0].type = key_type;
+        dst[0].flags = 0;
+        dst[0].length = 0;
+        dst[0].data.bits = g.key_bits;
+        for (int a = 0; a < plan->agg_count; a++) {
+            YtValue& v = dst[1 + a];
+            v.id = (uint16_t)(1 + a);
+            v.flags = 0;
+            v.length = 0;
+            if (plan->aggs[a]->func == YT_AGG_SUM1) {
+                v.type = YT_VT_INT64;
+                v.data.bits = g.cnt;
+            } else if (g.sum_nonnull == 0) {
+                v.type = YT_VT_NULL;
+                v.data.bits = 0;
+            } else {
+                v.type = sum_type[a];
+                v.data.bits = g.sum_bits;
+            }
+        }
+        return YT_OK;
+    };
+
     output->row_count = 0;
     output->column_count = out_cols;
     int rc = YT_OK;
@@ -2008,6 +2084,26 @@ static int emit_rows(const YtPlan* plan, const YtChunk* chunk,
             for (int t = 0; t < nt; t++) {
                 ths.emplace_back([&, t]() {
                     int64_t lo = ngroups * t / nt, hi = ngroups * (t + 1) / nt;
+                    if (slim) {
+                        /* slice by slice behind the copy: rows [lo, hi) */
+                        const int64_t per = slices ? slices->per : ngroups;
+                        for (int64_t a = lo; a < hi; ) {
+                            const int64_t sl = a / per;
+                            const int64_t b = std::min(hi, (sl + 1) * per);
+                            if (slices &&
+                                hipEventSynchronize(slices->ev[sl]) != hipSuccess) {
+                                arc.store(YT_ERR_HIP);
+                                return;
+                            }
+                            for (int64_t i = a; i < b; i++) {
+                                int r2 = emit_slim_at(output->values + i * out_cols,
+                                                      slim[i]);
+                                if (r2 != YT_OK) { arc.store(r2); return; }
+                            }
+                            a = b;
+                        }
+                        return;
+                    }
                     for (int64_t i = lo; i < hi; i++) {
                         const OutGroup& g = groups[i];
                         int r2 = emit_at(output->values + i * out_cols,
@@ -2020,6 +2116,22 @@ static int emit_rows(const YtPlan* plan, const YtChunk* chunk,
             for (auto& t : ths) t.join();
             if (arc.load() != YT_OK) return arc.load();
             output->row_count = ngroups;
+        } else if (slim) {
+            /* serial: output_row_limit, few groups, or a rowset too short */
+            if (slices && slices->count > 0 &&
+                hipEventSynchronize(slices->ev[slices->count - 1]) != hipSuccess)
+                return YT_ERR_HIP;
+            for (int64_t i = 0; i < ngroups; i++) {
+                if (output_row_limit > 0 && output->row_count >= output_row_limit) {
+                    if (out_limited) *out_limited = 1;
+                    return YT_OK;
+                }
+                if (output->row_count >= output->capacity_rows) return YT_ERR_CAPACITY;
+                rc = emit_slim_at(output->values + output->row_count * out_cols,
+                                  slim[i]);
+                if (rc) return rc;
+                output->row_count++;
+            }
         } else {
             for (int64_t i = 0; i < ngroups; i++) {
                 const OutGroup& g = groups[i];
@@ -4517,6 +4629,8 @@ extern "C" int yt_gpu_query_execute(
 
     DeviceRun R;
     R.stream = (hipStream_t)(uintptr_t)options->stream;
+    /* the groups go straight to the host from here: 32-byte records do */
+    R.want_slim = true;
     if (options->device) {
         hipError_t e = hipSetDevice(options->device);
         if (e != hipSuccess) { set_err(errbuf, errlen, "bad device"); return YT_ERR_HIP; }
@@ -4557,9 +4671,15 @@ extern "C" int yt_gpu_query_execute(
     /* compact + readback (pinned staging from the pool) */
     TableHdr th;
     OutGroup* hgroups = nullptr;
+    SlimGroup* hslim = nullptr;
+    SlimSlices slices;
+    slices.count = 0;
+    slices.per = 0;
     int64_t ngroups = 0;
     {
-        HIP_CHECK(hipMemcpy(&th, R.d_th, sizeof(th), hipMemcpyDeviceToHost));
+        /* the partitioned path already brought the header back */
+        if (R.th_valid) th = *R.h_th;
+        else HIP_CHECK(hipMemcpy(&th, R.d_th, sizeof(th), hipMemcpyDeviceToHost));
         if (th.overflow == 1) { set_err(errbuf, errlen, "group table overflow — raise max_groups_hint"); rc = YT_ERR_CAPACITY; goto fail; }
         ngroups = (int64_t)th.ngroups;
         if (ngroups > 0 && !R.groups_compacted) {
@@ -4569,7 +4689,24 @@ extern "C" int yt_gpu_query_execute(
             HIP_CHECK(ytql_launch_compact(nullptr, R.d_th, R.d_slots, plan->agg_count,
                                           R.d_groups, R.d_counter, R.nslots, R.stream));
         }
-        if (ngroups > 0) {
+        if (ngroups > 0 && R.groups_compacted && R.groups_slim) {
+            /* 32-byte records; from 65,536 groups on (where emit_rows may
+             * run its workers) in slices, so that the emit of one slice
+             * overlaps the copy of the next */
+            const SlimGroup* d_slim = (const SlimGroup*)R.d_groups;
+            HIP_CHECK(pool_alloc_host(&hslim, sizeof(SlimGroup) * ngroups));
+            const int want = ngroups >= 65536 ? kGroupSlices : 1;
+            slices.per = (ngroups + want - 1) / want;
+            for (int64_t a = 0; a < ngroups; a += slices.per) {
+                const int64_t cnt = std::min(slices.per, ngroups - a);
+                HIP_CHECK(hipMemcpyAsync(hslim + a, d_slim + a, sizeof(SlimGroup) * cnt,
+                                         hipMemcpyDeviceToHost, R.stream));
+                hipEvent_t ev = nullptr;
+                HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+                slices.ev[slices.count++] = ev;
+                HIP_CHECK(hipEventRecord(ev, R.stream));
+            }
+        } else if (ngroups > 0) {
             HIP_CHECK(pool_alloc_host(&hgroups, sizeof(OutGroup) * ngroups));
             HIP_CHECK(hipMemcpyAsync(hgroups, R.d_groups, sizeof(OutGroup) * ngroups,
                                      hipMemcpyDeviceToHost, R.stream));
@@ -4587,8 +4724,22 @@ extern "C" int yt_gpu_query_execute(
         rc = emit_rows(plan, chunk, &dp, hgroups, ngroups, th, 0, gaccum.data(),
                        fs.valid && fs.key_col < 0,
                        options->output_row_limit, &out_limited,
-                       output, errbuf, errlen);
+                       output, errbuf, errlen, hslim, hslim ? &slices : nullptr);
+        if (hslim) {
+            /* nothing may still be writing the staging buffer when the pool
+             * takes it back (emit_rows can return before the last slice) */
+            hipError_t es = hipStreamSynchronize(R.stream);
+            if (es != hipSuccess && rc == YT_OK) {
+                set_err(errbuf, errlen, hipGetErrorString(es));
+                rc = YT_ERR_HIP;
+            }
+        }
+        for (int i = 0; i < slices.count; i++) (void)hipEventDestroy(slices.ev[i]);
+        slices.count = 0;
         g_pool.put(hgroups);
+        g_pool.put(hslim);
+        hgroups = nullptr;
+        hslim = nullptr;
         if (rc) return rc;
         if (out_limited && stats) stats->incomplete_output = 1;
     }
@@ -4622,6 +4773,10 @@ extern "C" int yt_gpu_query_execute(
     }
     return YT_OK;
 fail:
+    if (hslim || hgroups) (void)hipStreamSynchronize(R.stream);
+    for (int i = 0; i < slices.count; i++) (void)hipEventDestroy(slices.ev[i]);
+    g_pool.put(hgroups);
+    g_pool.put(hslim);
     return rc;
 }
 

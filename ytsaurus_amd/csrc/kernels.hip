@@ -161,17 +161,14 @@ __device__ __forceinline__ uint64_t bp_gl(const uint64_t* base, uint64_t mask,
 /* ------------------------------------------------------------------ */
 /* segment header parsing (one thread per segment)                     */
 
-__global__ void k_parse_segments(const DevSeg* segs, int nsegs, SegEx* out,
-                                 unsigned* max_width_out,
-                                 unsigned* col_null_flags /* kMaxCols words */,
-                                 unsigned long long* col_zzmin /* kMaxCols, init ~0 */,
-                                 unsigned long long* col_zzmax /* kMaxCols, init 0 */)
+/* fills e from the segment's headers. Returns false for a STRING column's
+ * segment, which takes no part in the per-column words; otherwise true, with
+ * *nullbits = the bits the segment adds to its column's null flags. */
+__device__ __forceinline__ bool parse_segment(const DevSeg& s, SegEx& e,
+                                              unsigned* nullbits)
 {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nsegs) return;
-    const DevSeg& s = segs[i];
-    SegEx e = {};
     const uint64_t* b = s.blob;
+    *nullbits = 0;
     if (s.type == YT_SEG_DOUBLE) {
         /* [u64 count][doubles][null bitmap]. The blob's own count places the
          * bitmap: input_row_limit may have clamped s.row_count below it. */
@@ -263,8 +260,7 @@ __global__ void k_parse_segments(const DevSeg* segs, int nsegs, SegEx* out,
             e.flags |= 16;  /* unknown string layout: no GPU key path */
             break;
         }
-        out[i] = e;
-        return;
+        return false;
     } else if (s.type == YT_SEG_BOOLEAN) {
         /* [u64 count][value bitmap][null bitmap], both 8-aligned */
         e.off_doubles_bytes = 8;     /* value bitmap */
@@ -325,21 +321,123 @@ __global__ void k_parse_segments(const DevSeg* segs, int nsegs, SegEx* out,
     if (s.type != YT_SEG_DIRECT_DENSE && s.type != YT_SEG_DOUBLE) {
         /* dictionary/RLE null presence is unknown without an id scan —
          * be conservative (fast paths only run on DirectDense anyway) */
-        atomicOr(&col_null_flags[s.col], 2u);
+        *nullbits = 2u;
     }
-    out[i] = e;
-    atomicMax(max_width_out, e.w_values);
-    /* per-column zigzag-space range, from segment meta alone
-     * (value = min_value + packed, packed < 2^w) */
-    {
-        unsigned long long lo = (unsigned long long)s.min_value;
-        unsigned long long span = (e.w_values >= 64) ? ~0ULL
-                                : ((1ULL << e.w_values) - 1);
-        unsigned long long hi = lo + span;   /* may wrap for degenerate metas */
-        if (hi < lo) hi = ~0ULL;
-        atomicMin(&col_zzmin[s.col], lo);
-        atomicMax(&col_zzmax[s.col], hi);
+    return true;
+}
+
+/* The per-column words (null flags, zigzag min / max) and the widest value
+ * vector are combined within the wave before the global atomics: segments
+ * arrive in column order, so a wave holds one or two distinct columns and
+ * issues a handful of atomics where every thread used to issue four on the
+ * same few addresses. */
+__global__ void k_parse_segments(const DevSeg* segs, int nsegs, SegEx* out,
+                                 unsigned* max_width_out,
+                                 unsigned* col_null_flags /* kMaxCols words */,
+                                 unsigned long long* col_zzmin /* kMaxCols, init ~0 */,
+                                 unsigned long long* col_zzmax /* kMaxCols, init 0 */)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int col = -1;               /* -1: nothing to contribute */
+    unsigned nullbits = 0, width = 0;
+    unsigned long long lo = ~0ULL, hi = 0;
+    if (i < nsegs) {
+        const DevSeg& s = segs[i];
+        SegEx e = {};
+        const bool counts = parse_segment(s, e, &nullbits);
+        out[i] = e;
+        if (counts) {
+            col = s.col;
+            width = e.w_values;
+            /* per-column zigzag-space range, from segment meta alone
+             * (value = min_value + packed, packed < 2^w) */
+            lo = (unsigned long long)s.min_value;
+            unsigned long long span = (e.w_values >= 64) ? ~0ULL
+                                    : ((1ULL << e.w_values) - 1);
+            hi = lo + span;   /* may wrap for degenerate metas */
+            if (hi < lo) hi = ~0ULL;
+        }
     }
+    unsigned wmax = width;
+    for (int sh = 32; sh >= 1; sh >>= 1)
+        wmax = max(wmax, (unsigned)__shfl_xor((int)wmax, sh, 64));
+    unsigned long long todo = __ballot(col >= 0);
+    if (lane == 0 && todo) atomicMax(max_width_out, wmax);
+    while (todo) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const int c = __shfl(col, leader, 64);
+        const bool mine = (col == c);
+        unsigned nb = mine ? nullbits : 0u;
+        unsigned long long mn = mine ? lo : ~0ULL;
+        unsigned long long mx = mine ? hi : 0ULL;
+        for (int sh = 32; sh >= 1; sh >>= 1) {
+            nb |= (unsigned)__shfl_xor((int)nb, sh, 64);
+            mn = min(mn, (unsigned long long)__shfl_xor((long long)mn, sh, 64));
+            mx = max(mx, (unsigned long long)__shfl_xor((long long)mx, sh, 64));
+        }
+        if (lane == leader) {
+            if (nb) atomicOr(&col_null_flags[c], nb);
+            atomicMin(&col_zzmin[c], mn);
+            atomicMax(&col_zzmax[c], mx);
+        }
+        todo &= ~__ballot(mine);
+    }
+}
+
+/* k_scan_zzrange's stream over one segment's packed words (width 1..64; T
+ * holds a value: uint32_t up to width 32). A thread takes whole words, 256
+ * apart, and extracts the values that START in its word (v = the first of
+ * them, sb = its bit in the word); a value that runs over the word's end
+ * takes its top bits from the next word, which may be the one past the
+ * vector. Stepping 256 words = 16384 bits = q * w + r moves (v, sb) without
+ * dividing. Rows from n on do not count. */
+template <typename T>
+__device__ __forceinline__ void zz_stream(const uint64_t* words, const uint64_t* bm64,
+                                          uint32_t n, uint32_t w, uint32_t tid,
+                                          T& mn, T& mx)
+{
+    const T mask = (w >= 8 * sizeof(T)) ? (T)~(T)0 : (T)(((T)1 << w) - 1);
+    const int64_t nwords = ((int64_t)n * w + 63) >> 6;
+    const uint32_t q = 16384u / w, r = 16384u % w;
+    uint32_t v = (64u * tid + w - 1) / w;
+    uint32_t sb = v * w - 64u * tid;
+    auto take = [&](uint64_t lo, uint64_t hi) {
+        if (v < n) {
+            uint64_t nb = 0;
+            if (bm64) {
+                /* null bits of the rows from v on: 64 cover a word's values */
+                const unsigned sh = v & 63;
+                nb = bm64[v >> 6] >> sh;
+                const uint32_t last = min(v + (63u - sb) / w, n - 1);
+                if ((last >> 6) != (v >> 6)) nb |= bm64[last >> 6] << (64 - sh);
+            }
+            /* a word starts at most 64 values: with 64 rows left, no row check */
+            const uint32_t bend = (n - v >= 64u) ? 64u : min(64u, sb + (n - v) * w);
+            for (uint32_t b = sb; b < bend; b += w, nb >>= 1) {
+                T z = (T)(lo >> b);
+                if (b + w > 64) z |= (T)((T)hi << (64 - b));
+                z &= mask;
+                if (!(nb & 1)) { mn = min(mn, z); mx = max(mx, z); }
+            }
+        }
+        /* the next word of this thread, 16384 bits on */
+        if (sb >= r) { v += q; sb -= r; }
+        else { v += q + 1; sb += w - r; }
+    };
+    int64_t i = tid;
+    for (; i + 768 < nwords; i += 1024) {
+        /* eight independent loads in flight before the first use */
+        const uint64_t a0 = words[i], b0 = words[i + 1];
+        const uint64_t a1 = words[i + 256], b1 = words[i + 257];
+        const uint64_t a2 = words[i + 512], b2 = words[i + 513];
+        const uint64_t a3 = words[i + 768], b3 = words[i + 769];
+        take(a0, b0);
+        take(a1, b1);
+        take(a2, b2);
+        take(a3, b3);
+    }
+    for (; i < nwords; i += 256) take(words[i], words[i + 1]);
 }
 
 /* exact zigzag-space min/max of one DirectDense int64 column (non-null
@@ -348,7 +446,10 @@ __global__ void k_parse_segments(const DevSeg* segs, int nsegs, SegEx* out,
  * disable packed records / direct-span mode on data that
  * actually fits (the headline config: 21+41 = 62 real bits, 22+42 = 64 by
  * meta). One workgroup per segment; out[0] = min (init ~0), out[1] = max
- * (init 0). */
+ * (init 0); no update when every value is null. The packed words are
+ * streamed: each is loaded about once, coalesced, and every value is taken
+ * from registers (a load pair per VALUE, as bp_gl does it, left the kernel
+ * bound by load instructions at a third of the HBM rate). */
 __global__ void __launch_bounds__(256)
 k_scan_zzrange(const DevSeg* segs, const SegEx* segex, int seg_off,
                int has_nulls, unsigned long long* out)
@@ -359,25 +460,26 @@ k_scan_zzrange(const DevSeg* segs, const SegEx* segex, int seg_off,
     const SegEx& e = segex[si];
     const uint64_t* words = s.blob + e.off_values_words;
     const uint32_t w = e.w_values;
-    const uint64_t mask = (w >= 64) ? ~0ULL : ((1ULL << w) - 1);
     const uint8_t* bm = has_nulls
         ? (const uint8_t*)s.blob + e.off_bitmap_bytes : nullptr;
+    const uint64_t* bm64 = (const uint64_t*)bm;   /* 8-aligned, zero-padded to 8 */
     uint64_t mn = ~0ULL, mx = 0;
-    const int n = s.row_count;
-    int64_t j = threadIdx.x;
-    for (; j + 1792 < n; j += 2048) {
-        #pragma unroll
-        for (int u = 0; u < 8; u++) {
-            int64_t jj = j + u * 256;
-            uint64_t z = bp_gl(words, mask, w, jj);
-            if (!bm || !bm_get(bm, jj)) { mn = min(mn, z); mx = max(mx, z); }
+    const uint32_t n = (uint32_t)s.row_count;
+    if (w == 0) {
+        /* every packed value is 0: the range is {0} once one row is non-null */
+        bool any = false;
+        if (!bm) any = n > 0;
+        else for (uint32_t j = threadIdx.x; j < n; j += 256) any |= !bm_get(bm, j);
+        if (any) { mn = 0; mx = 0; }
+    } else {
+        /* widths up to 32 keep their values, minimum and maximum in 32 bits */
+        if (w <= 32) {
+            uint32_t mn32 = ~0u, mx32 = 0;
+            zz_stream<uint32_t>(words, bm64, n, w, threadIdx.x, mn32, mx32);
+            if (mn32 <= mx32) { mn = mn32; mx = mx32; }   /* saw a value */
+        } else {
+            zz_stream<uint64_t>(words, bm64, n, w, threadIdx.x, mn, mx);
         }
-    }
-    for (; j < n; j += 256) {
-        if (bm && bm_get(bm, j)) continue;
-        uint64_t z = bp_gl(words, mask, w, j);
-        mn = min(mn, z);
-        mx = max(mx, z);
     }
     for (int sh = 32; sh >= 1; sh >>= 1) {
         mn = min(mn, (uint64_t)__shfl_down((long long)mn, sh, 64));
@@ -2228,14 +2330,15 @@ k_scan_partition(PartParams pp, const DevSeg* segs, const SegEx* segex,
 
 /* Phase B: one workgroup per bucket. LDS table slot = {key, cnt|nonnull<<32
  * packed, sum}; per-workgroup counts stay < 2^32 because a bucket's rows do.
- * Emits compacted OutGroups directly (buckets are key-disjoint). */
+ * Emits compacted OutGroups directly (buckets are key-disjoint), or
+ * SlimGroups (out then points at those) when the launcher sets slim. */
 __global__ void __launch_bounds__(256)
 k_bucket_agg(const ulonglong2* recs, const unsigned long long* cursors,
              int64_t bucket_stride,
              const uint64_t* nrecs, const unsigned long long* ncursors,
              int64_t nbucket_stride,
              OutGroup* out, unsigned long long* out_counter, int64_t out_cap,
-             TableHdr* th, int sum_slot, int agg_count,
+             int slim, TableHdr* th, int sum_slot, int agg_count,
              int packed_mode, int bits_k, uint64_t gmin_k, uint64_t gmin_v,
              int nsub)
 {
@@ -2369,6 +2472,14 @@ k_bucket_agg(const ulonglong2* recs, const unsigned long long* cursors,
         unsigned long long t = atomicAdd(&th->ngroups, 1ULL);
         if (th->group_limit > 0 && (int64_t)t >= th->group_limit) mark_group_limit(th);
         if ((int64_t)idx >= out_cap) { th->overflow = 1; continue; }
+        if (slim) {
+            const uint64_t cn = tab[i * 3 + 1];
+            ulonglong2* g2 = (ulonglong2*)((SlimGroup*)out + idx);
+            g2[0] = make_ulonglong2(key, cn & 0xFFFFFFFFULL);
+            g2[1] = sum_slot >= 0 ? make_ulonglong2(tab[i * 3 + 2], cn >> 32)
+                                  : make_ulonglong2(0, 0);
+            continue;
+        }
         OutGroup& g = out[idx];
         g.key_bits = key;
         g.key_meta = 0;
@@ -2397,7 +2508,7 @@ k_bucket_agg_direct(const ulonglong2* recs, const unsigned long long* cursors,
                     const uint64_t* nrecs, const unsigned long long* ncursors,
                     int64_t nbucket_stride,
                     OutGroup* out, unsigned long long* out_counter, int64_t out_cap,
-                    TableHdr* th, int sum_slot, int agg_count,
+                    int slim, TableHdr* th, int sum_slot, int agg_count,
                     int packed_mode, int bits_k, uint64_t gmin_k, uint64_t gmin_v,
                     int dshift, int nsub)
 {
@@ -2506,6 +2617,14 @@ k_bucket_agg_direct(const ulonglong2* recs, const unsigned long long* cursors,
         unsigned long long t = atomicAdd(&th->ngroups, 1ULL);
         if (th->group_limit > 0 && (int64_t)t >= th->group_limit) mark_group_limit(th);
         if ((int64_t)idx >= out_cap) { th->overflow = 1; continue; }
+        if (slim) {
+            ulonglong2* g2 = (ulonglong2*)((SlimGroup*)out + idx);
+            g2[0] = make_ulonglong2((uint64_t)zz_dec(gmin_k + base_rel + (uint64_t)i),
+                                    cn & 0xFFFFFFFFULL);
+            g2[1] = sum_slot >= 0 ? make_ulonglong2(sums[i], cn >> 32)
+                                  : make_ulonglong2(0, 0);
+            continue;
+        }
         OutGroup& g = out[idx];
         g.key_bits = (uint64_t)zz_dec(gmin_k + base_rel + (uint64_t)i);
         g.key_meta = 0;
@@ -4185,7 +4304,7 @@ hipError_t ytql_launch_bucket_agg(const void* recs, const unsigned long long* cu
                                   const uint64_t* nrecs, const unsigned long long* ncursors,
                                   int64_t nbucket_stride,
                                   OutGroup* out, unsigned long long* out_counter,
-                                  int64_t out_cap,
+                                  int64_t out_cap, int slim,
                                   TableHdr* th, int sum_slot, int agg_count,
                                   int packed_mode, int bits_k,
                                   uint64_t gmin_k, uint64_t gmin_v,
@@ -4194,7 +4313,7 @@ hipError_t ytql_launch_bucket_agg(const void* recs, const unsigned long long* cu
     hipLaunchKernelGGL(k_bucket_agg, dim3(kNB), dim3(256), 0, st,
                        (const ulonglong2*)recs, cursors, bucket_stride,
                        nrecs, ncursors, nbucket_stride,
-                       out, out_counter, out_cap, th, sum_slot, agg_count,
+                       out, out_counter, out_cap, slim, th, sum_slot, agg_count,
                        packed_mode, bits_k, gmin_k, gmin_v, nsub);
     return hipGetLastError();
 }
@@ -4204,7 +4323,7 @@ hipError_t ytql_launch_bucket_agg_direct(const void* recs, const unsigned long l
                                          const uint64_t* nrecs, const unsigned long long* ncursors,
                                          int64_t nbucket_stride,
                                          OutGroup* out, unsigned long long* out_counter,
-                                         int64_t out_cap,
+                                         int64_t out_cap, int slim,
                                          TableHdr* th, int sum_slot, int agg_count,
                                          int packed_mode, int bits_k,
                                          uint64_t gmin_k, uint64_t gmin_v,
@@ -4214,7 +4333,7 @@ hipError_t ytql_launch_bucket_agg_direct(const void* recs, const unsigned long l
     hipLaunchKernelGGL(k_bucket_agg_direct, dim3(kNB), dim3(256), lds, st,
                        (const ulonglong2*)recs, cursors, bucket_stride,
                        nrecs, ncursors, nbucket_stride,
-                       out, out_counter, out_cap, th, sum_slot, agg_count,
+                       out, out_counter, out_cap, slim, th, sum_slot, agg_count,
                        packed_mode, bits_k, gmin_k, gmin_v, dshift, nsub);
     return hipGetLastError();
 }
