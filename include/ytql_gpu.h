@@ -524,6 +524,12 @@ int32_t yt_gpu_debug_partition_tile_rows(int large);
  * summed over its predicates; 0 when it had none. */
 uint64_t yt_gpu_debug_last_strpred_entries(void);
 
+/* Diagnostic only: blocks of the library's device/pinned buffer pool that
+ * are taken and not yet given back, over all threads. A finished call holds
+ * none, except what it handed out (a yt_gpu_versioned_scan_chunk handle until
+ * yt_gpu_scan_chunk_free), so the value is the same before and after it. */
+uint64_t yt_gpu_debug_pool_blocks_in_use(void);
+
 /* Two-phase (coordinated) path, mirroring the bottom/front query split
  * (engine_api/coordinator.h:26,78,89; shuffle engine_api/shuffling_reader.cpp:21-88).
  *

@@ -244,6 +244,7 @@ def gpu_lib():
         _sig(lib, "yt_gpu_debug_last_scan_path", C.c_uint32, [])
         _sig(lib, "yt_gpu_debug_partition_tile_rows", C.c_int32, [C.c_int])
         _sig(lib, "yt_gpu_debug_last_strpred_entries", C.c_uint64, [])
+        _sig(lib, "yt_gpu_debug_pool_blocks_in_use", C.c_uint64, [])
         _sig(lib, "yt_strpred_eval", C.c_int,
              [C.c_int, C.c_int, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64])
         _sig(lib, "yt_gpu_query_partial", C.c_int,

@@ -19,6 +19,7 @@
 #include <chrono>
 #include <thread>
 #include <atomic>
+#include <memory>
 
 #include "common.h"
 #include "strpred.h"
@@ -271,21 +272,86 @@ struct Pool {
                                   [](const Blk& b) { return !b.p; }),
                    blks.end());
     }
+
+    uint64_t in_use()
+    {
+        std::lock_guard<std::mutex> g(m);
+        uint64_t n = 0;
+        for (auto& b : blks) n += b.used;
+        return n;
+    }
 };
 
 Pool g_pool;
 
-template <class T>
-hipError_t pool_alloc(T** p, size_t sz)
-{
-    return g_pool.get(sz, false, (void**)p);
-}
+/* The owner of what a call takes from g_pool and of the events it creates:
+ * the destructor destroys the events, then puts every block back, so no exit
+ * has a list to repeat. The call sites keep their raw pointers. */
+struct PoolScope {
+    std::vector<void*> blks;
+    std::vector<hipEvent_t> evs;
 
-template <class T>
-hipError_t pool_alloc_host(T** p, size_t sz)
-{
-    return g_pool.get(sz, true, (void**)p);
-}
+    PoolScope() = default;
+    PoolScope(const PoolScope&) = delete;
+    PoolScope& operator=(const PoolScope&) = delete;
+
+    ~PoolScope()
+    {
+        for (hipEvent_t e : evs) (void)hipEventDestroy(e);
+        for (void* b : blks) g_pool.put(b);
+    }
+
+    template <class T>
+    hipError_t dev(T** p, size_t bytes) { return take((void**)p, bytes, false); }
+
+    template <class T>
+    hipError_t host(T** p, size_t bytes) { return take((void**)p, bytes, true); }
+
+    /* put one block back early; null and unknown pointers are ignored */
+    void release(void* p) { if (forget(p)) g_pool.put(p); }
+
+    /* the block outlives the call: its new owner puts it back */
+    void detach(void* p) { (void)forget(p); }
+
+    hipError_t event(hipEvent_t* e, unsigned flags = hipEventDefault)
+    {
+        hipError_t err = hipEventCreateWithFlags(e, flags);
+        if (err == hipSuccess) evs.push_back(*e);
+        return err;
+    }
+
+private:
+    hipError_t take(void** p, size_t bytes, bool host)
+    {
+        hipError_t err = g_pool.get(bytes, host, p);
+        if (err == hipSuccess) blks.push_back(*p);
+        return err;
+    }
+
+    bool forget(void* p)
+    {
+        auto it = p ? std::find(blks.begin(), blks.end(), p) : blks.end();
+        if (it == blks.end()) return false;
+        blks.erase(it);
+        return true;
+    }
+};
+
+/* joins its threads on every way out of the scope that holds it */
+struct ThreadJoiner {
+    std::vector<std::thread> ths;
+
+    ThreadJoiner() = default;
+    ThreadJoiner(const ThreadJoiner&) = delete;
+    ThreadJoiner& operator=(const ThreadJoiner&) = delete;
+    ~ThreadJoiner() { join(); }
+
+    void join()
+    {
+        for (auto& t : ths) if (t.joinable()) t.join();
+        ths.clear();
+    }
+};
 
 double now_ms()
 {
@@ -300,6 +366,12 @@ extern "C" void yt_gpu_pool_trim(void)
     g_pool.trim();
 }
 
+/* diagnostic: pool blocks taken and not yet put back */
+extern "C" uint64_t yt_gpu_debug_pool_blocks_in_use(void)
+{
+    return g_pool.in_use();
+}
+
 static void set_err(char* errbuf, size_t errlen, const char* msg)
 {
     if (errbuf && errlen) snprintf(errbuf, errlen, "%s", msg);
@@ -311,8 +383,7 @@ static void set_err(char* errbuf, size_t errlen, const char* msg)
         if (e_ != hipSuccess) {                                             \
             if (errbuf) snprintf(errbuf, errlen, "HIP error %s at %s:%d",   \
                                  hipGetErrorString(e_), __FILE__, __LINE__);\
-            rc = YT_ERR_HIP;                                                \
-            goto fail;                                                      \
+            return YT_ERR_HIP;                                              \
         }                                                                   \
     } while (0)
 
@@ -433,13 +504,8 @@ struct StrPreds {
     int count = 0;                  /* leaves that need a bitmap */
     bool any = false;               /* any leaf, bitmap-less ones included */
     StrPredDesc d[kMaxStrPreds];
-    std::vector<void*> bufs;        /* pooled device buffers of this run */
+    PoolScope ps;                   /* pooled device buffers of this run */
     std::vector<int64_t> h_base[kMaxStrPreds];   /* upload sources */
-
-    ~StrPreds()
-    {
-        for (void* b : bufs) g_pool.put(b);
-    }
 };
 
 static thread_local uint64_t t_last_strpred_entries = 0;
@@ -1115,27 +1181,7 @@ struct DeviceRun {
     uint64_t col_zzmin[kMaxCols] = {0};
     uint64_t col_zzmax[kMaxCols] = {0};
     hipStream_t stream = 0;
-
-    ~DeviceRun()
-    {
-        g_pool.put(d_segs);
-        g_pool.put(d_segex);
-        g_pool.put(d_off);
-        g_pool.put(d_cnt);
-        g_pool.put(d_setup);
-        g_pool.put(h_setup);
-        g_pool.put(d_th);
-        g_pool.put(d_slots);
-        g_pool.put(d_groups);
-        g_pool.put(d_counter);
-        g_pool.put(d_gaccum);
-        g_pool.put(d_fastcols);
-        g_pool.put(d_cursors);
-        g_pool.put(d_recs);
-        g_pool.put(d_ncursors);
-        g_pool.put(d_nrecs);
-        g_pool.put(h_th);
-    }
+    PoolScope ps;                      /* owns every block above */
 };
 
 /* diagnostic: which scan path the last query on this thread took
@@ -1169,7 +1215,6 @@ static int setup_chunk(const YtChunk* chunk, DeviceRun* R, unsigned* maxw_out,
                        int64_t input_row_limit, int* clamped,
                        char* errbuf, size_t errlen)
 {
-    int rc = YT_OK;
     int ncols = chunk->column_count;
     if (clamped) *clamped = 0;
     R->h_off.resize(ncols);
@@ -1216,15 +1261,15 @@ static int setup_chunk(const YtChunk* chunk, DeviceRun* R, unsigned* maxw_out,
     R->nsegs = (int)R->h_segs.size();
     if (R->nsegs == 0) return YT_OK;
 
-    HIP_CHECK(pool_alloc(&R->d_segs, sizeof(DevSeg) * R->nsegs));
-    HIP_CHECK(pool_alloc(&R->d_segex, sizeof(SegEx) * R->nsegs));
-    HIP_CHECK(pool_alloc(&R->d_off, sizeof(int32_t) * ncols));
-    HIP_CHECK(pool_alloc(&R->d_cnt, sizeof(int32_t) * ncols));
+    HIP_CHECK(R->ps.dev(&R->d_segs, sizeof(DevSeg) * R->nsegs));
+    HIP_CHECK(R->ps.dev(&R->d_segex, sizeof(SegEx) * R->nsegs));
+    HIP_CHECK(R->ps.dev(&R->d_off, sizeof(int32_t) * ncols));
+    HIP_CHECK(R->ps.dev(&R->d_cnt, sizeof(int32_t) * ncols));
     /* the scalar words: one block, set by one copy of a pinned host image
      * and read back into it by one copy (it was five fills and four copies
      * into pageable memory) */
-    HIP_CHECK(pool_alloc(&R->d_setup, sizeof(SetupWords)));
-    HIP_CHECK(pool_alloc_host(&R->h_setup, sizeof(SetupWords)));
+    HIP_CHECK(R->ps.dev(&R->d_setup, sizeof(SetupWords)));
+    HIP_CHECK(R->ps.host(&R->h_setup, sizeof(SetupWords)));
     R->d_maxw = &R->d_setup->maxw;
     R->d_err = R->d_setup->err;
     R->d_colnull = R->d_setup->col_null;
@@ -1255,8 +1300,6 @@ static int setup_chunk(const YtChunk* chunk, DeviceRun* R, unsigned* maxw_out,
     memcpy(R->col_zzmin, R->h_setup->zzmin, sizeof(R->col_zzmin));
     memcpy(R->col_zzmax, R->h_setup->zzmax, sizeof(R->col_zzmax));
     return YT_OK;
-fail:
-    return rc;
 }
 
 /* String predicates, after setup_chunk: for every predicate read back its
@@ -1267,7 +1310,7 @@ fail:
 static int setup_string_preds(StrPreds* sp, DeviceRun* R, DevPlan* dp,
                               char* errbuf, size_t errlen)
 {
-    int rc = YT_OK;
+    PoolScope ps;                   /* the two timing events */
     uint64_t entries = 0;
     const bool timing = getenv("YTQL_TIMING") != nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1275,8 +1318,8 @@ static int setup_string_preds(StrPreds* sp, DeviceRun* R, DevPlan* dp,
     dp->sp_count = sp->count;
     if (sp->count == 0 || R->nsegs == 0) return YT_OK;
     if (timing) {
-        HIP_CHECK(hipEventCreate(&e0));
-        HIP_CHECK(hipEventCreate(&e1));
+        HIP_CHECK(ps.event(&e0));
+        HIP_CHECK(ps.event(&e1));
         HIP_CHECK(hipEventRecord(e0, R->stream));
     }
     for (int i = 0; i < sp->count; i++) {
@@ -1293,8 +1336,7 @@ static int setup_string_preds(StrPreds* sp, DeviceRun* R, DevPlan* dp,
             if (!(ex[sg].flags & (8 | 32 | 64))) {
                 set_err(errbuf, errlen,
                         "string predicate: unknown string segment layout");
-                rc = YT_ERR_UNSUPPORTED;
-                goto fail;
+                return YT_ERR_UNSUPPORTED;
             }
             base[sg] = words;
             words += ((int64_t)ex[sg].dict_size + 63) / 64;
@@ -1304,12 +1346,9 @@ static int setup_string_preds(StrPreds* sp, DeviceRun* R, DevPlan* dp,
         int64_t* d_base = nullptr;
         uint64_t* d_bits = nullptr;
         char* d_lit = nullptr;
-        HIP_CHECK(pool_alloc(&d_base, sizeof(int64_t) * (cnt + 1)));
-        sp->bufs.push_back(d_base);
-        HIP_CHECK(pool_alloc(&d_bits, sizeof(uint64_t) * (words ? words : 1)));
-        sp->bufs.push_back(d_bits);
-        HIP_CHECK(pool_alloc(&d_lit, (size_t)(d.lit_len ? d.lit_len : 1)));
-        sp->bufs.push_back(d_lit);
+        HIP_CHECK(sp->ps.dev(&d_base, sizeof(int64_t) * (cnt + 1)));
+        HIP_CHECK(sp->ps.dev(&d_bits, sizeof(uint64_t) * (words ? words : 1)));
+        HIP_CHECK(sp->ps.dev(&d_lit, (size_t)(d.lit_len ? d.lit_len : 1)));
         HIP_CHECK(hipMemcpyAsync(d_base, base.data(), sizeof(int64_t) * (cnt + 1),
                                  hipMemcpyHostToDevice, R->stream));
         if (d.lit_len)
@@ -1333,19 +1372,15 @@ static int setup_string_preds(StrPreds* sp, DeviceRun* R, DevPlan* dp,
                         "entry pass %.3fms\n",
                 sp->count, (unsigned long long)entries, ms);
     }
-fail:
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
+    return YT_OK;
 }
 
 static int setup_table(DeviceRun* R, int agg_count, int64_t max_groups,
                        int64_t group_limit, char* errbuf, size_t errlen)
 {
-    int rc = YT_OK;
     R->nslots = next_pow2((uint64_t)(max_groups > 0 ? max_groups : (1 << 20)) * 2);
     if (R->nslots < 2048) R->nslots = 2048;
-    HIP_CHECK(pool_alloc(&R->d_th, sizeof(TableHdr)));
+    HIP_CHECK(R->ps.dev(&R->d_th, sizeof(TableHdr)));
     TableHdr hh;
     memset(&hh, 0, sizeof(hh));
     hh.nslots = R->nslots;
@@ -1353,21 +1388,16 @@ static int setup_table(DeviceRun* R, int agg_count, int64_t max_groups,
     hh.group_limit = group_limit;
     HIP_CHECK(hipMemcpyAsync(R->d_th, &hh, sizeof(hh), hipMemcpyHostToDevice, R->stream));
     return YT_OK;
-fail:
-    return rc;
 }
 
 /* the direct-table slot array is only needed on the non-partitioned paths */
 static int ensure_slots(DeviceRun* R, int agg_count, char* errbuf, size_t errlen)
 {
-    int rc = YT_OK;
     if (R->d_slots) return YT_OK;
     int stride = 2 + 2 * agg_count;
-    HIP_CHECK(pool_alloc(&R->d_slots, sizeof(uint64_t) * R->nslots * stride));
+    HIP_CHECK(R->ps.dev(&R->d_slots, sizeof(uint64_t) * R->nslots * stride));
     HIP_CHECK(hipMemsetAsync(R->d_slots, 0, sizeof(uint64_t) * R->nslots * stride, R->stream));
     return YT_OK;
-fail:
-    return rc;
 }
 
 /* Two-phase partitioned group-by for the {1 direct int64 key, <=1 direct
@@ -1384,6 +1414,7 @@ static int run_partitioned(const YtPlan* plan, const YtChunk* chunk,
 {
     int rc = YT_OK;
     *done = false;
+    PoolScope ps;                   /* the events; the blocks are R's */
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
     uint32_t path = YT_SCAN_PATH_PARTITIONED
                   | (force_hash ? YT_SCAN_PATH_HASH_RETRY : 0);
@@ -1419,7 +1450,7 @@ static int run_partitioned(const YtPlan* plan, const YtChunk* chunk,
             /* refine the meta-only span (rounded up to min+2^w-1 per
              * segment) by an exact device scan of the column */
             uint64_t* d_ex = nullptr;
-            int rc2 = pool_alloc(&d_ex, 2 * sizeof(uint64_t));
+            int rc2 = ps.dev(&d_ex, 2 * sizeof(uint64_t));
             if (rc2 != YT_OK) return rc2;
             uint64_t init[2] = { ~0ULL, 0 };
             hipError_t e;
@@ -1432,11 +1463,11 @@ static int run_partitioned(const YtPlan* plan, const YtChunk* chunk,
                 (e = hipMemcpyAsync(init, d_ex, sizeof(init),
                                     hipMemcpyDeviceToHost, R->stream)) ||
                 (e = hipStreamSynchronize(R->stream))) {
-                g_pool.put(d_ex);
+                ps.release(d_ex);
                 set_err(errbuf, errlen, hipGetErrorString(e));
                 return YT_ERR_HIP;
             }
-            g_pool.put(d_ex);
+            ps.release(d_ex);
             if (init[0] <= init[1]) {   /* any non-null value seen */
                 R->col_zzmin[col] = init[0];
                 R->col_zzmax[col] = init[1];
@@ -1544,109 +1575,99 @@ static int run_partitioned(const YtPlan* plan, const YtChunk* chunk,
         fc[u].seg_cnt = R->h_cnt[used[u]];
     }
 
-    {
-        HIP_CHECK(pool_alloc(&R->d_fastcols, sizeof(FastCol) * nused));
-        HIP_CHECK(hipMemcpyAsync(R->d_fastcols, fc.data(), sizeof(FastCol) * nused,
-                                 hipMemcpyHostToDevice, R->stream));
-        HIP_CHECK(pool_alloc(&R->d_cursors, sizeof(uint64_t) * kNB * nsub));
-        HIP_CHECK(hipMemsetAsync(R->d_cursors, 0, sizeof(uint64_t) * kNB * nsub, R->stream));
-        HIP_CHECK(pool_alloc(&R->d_recs,
-                             (size_t)kNB * nsub * pp.bucket_stride * (pp.packed_mode ? 8 : 16)));
-        if (pp.has_val_nulls) {
-            HIP_CHECK(pool_alloc(&R->d_ncursors, sizeof(uint64_t) * kNB * 8));
-            HIP_CHECK(hipMemsetAsync(R->d_ncursors, 0, sizeof(uint64_t) * kNB * 8, R->stream));
-            HIP_CHECK(pool_alloc(&R->d_nrecs, (size_t)kNB * 8 * pp.nbucket_stride * 8));
-        }
-        /* the partitioned path's in-table sentinel is INT64_MIN bits */
-        uint64_t sk = kEmptyKey;
-        HIP_CHECK(hipMemcpyAsync((char*)R->d_th + offsetof(TableHdr, side_key_bits),
-                                 &sk, 8, hipMemcpyHostToDevice, R->stream));
-
-        int64_t cap_groups = (int64_t)kNB * kHSlots;
-        if (options->max_groups_hint > 0) {
-            int64_t want = options->max_groups_hint * 2 + 4096;
-            if (want < cap_groups) cap_groups = want;
-        }
-        if (cap_groups > rows + 16) cap_groups = rows + 16;
-        R->groups_capacity = cap_groups;
-        const int slim = R->want_slim ? 1 : 0;
-        HIP_CHECK(pool_alloc(&R->d_groups,
-                             (slim ? sizeof(SlimGroup) : sizeof(OutGroup)) * cap_groups));
-        if (!R->h_th) HIP_CHECK(pool_alloc_host(&R->h_th, sizeof(TableHdr)));
-        R->th_valid = false;
-        HIP_CHECK(pool_alloc(&R->d_counter, sizeof(unsigned long long)));
-        HIP_CHECK(hipMemsetAsync(R->d_counter, 0, sizeof(unsigned long long), R->stream));
-
-        HIP_CHECK(hipEventCreate(&ev0));
-        HIP_CHECK(hipEventCreate(&ev1));
-        HIP_CHECK(hipEventCreate(&ev2));
-        HIP_CHECK(hipEventRecord(ev0, R->stream));
-        HIP_CHECK(ytql_launch_scan_partition(&pp, R->d_segs, R->d_segex, R->d_fastcols,
-                                             R->d_th, R->d_cursors, R->d_recs,
-                                             R->d_ncursors, R->d_nrecs,
-                                             grid, R->stream));
-        HIP_CHECK(hipEventRecord(ev1, R->stream));
-        if (pp.direct_mode) {
-            HIP_CHECK(ytql_launch_bucket_agg_direct(R->d_recs, R->d_cursors, pp.bucket_stride,
-                                             R->d_nrecs, R->d_ncursors, pp.nbucket_stride,
-                                             R->d_groups, R->d_counter, cap_groups, slim,
-                                             R->d_th, pp.sum_slot, pp.agg_count,
-                                             pp.packed_mode, pp.bits_k,
-                                             pp.gmin_k, pp.gmin_v, pp.dshift, nsub, R->stream));
-        } else {
-            HIP_CHECK(ytql_launch_bucket_agg(R->d_recs, R->d_cursors, pp.bucket_stride,
-                                             R->d_nrecs, R->d_ncursors, pp.nbucket_stride,
-                                             R->d_groups, R->d_counter, cap_groups, slim,
-                                             R->d_th, pp.sum_slot, pp.agg_count,
-                                             pp.packed_mode, pp.bits_k,
-                                             pp.gmin_k, pp.gmin_v, nsub, R->stream));
-        }
-        HIP_CHECK(hipEventRecord(ev2, R->stream));
-        /* the header rides the synchronisation that the events need anyway */
-        HIP_CHECK(hipMemcpyAsync(R->h_th, R->d_th, sizeof(TableHdr),
-                                 hipMemcpyDeviceToHost, R->stream));
-        HIP_CHECK(hipStreamSynchronize(R->stream));
-        float msA = 0, msB = 0;
-        HIP_CHECK(hipEventElapsedTime(&msA, ev0, ev1));
-        HIP_CHECK(hipEventElapsedTime(&msB, ev1, ev2));
-        if (stats) {
-            stats->kernel_scan_ms += msA;
-            stats->kernel_scan_launches += 1;
-            stats->kernel_other_ms += msB;
-        }
-        /* overflow==1 → capacity guard; retry on the direct path */
-        if (R->h_th->overflow == 1) {
-            /* reset and fall back */
-            g_pool.put(R->d_groups); R->d_groups = nullptr;
-            g_pool.put(R->d_counter); R->d_counter = nullptr;
-            g_pool.put(R->d_recs); R->d_recs = nullptr;
-            g_pool.put(R->d_cursors); R->d_cursors = nullptr;
-            g_pool.put(R->d_nrecs); R->d_nrecs = nullptr;
-            g_pool.put(R->d_ncursors); R->d_ncursors = nullptr;
-            g_pool.put(R->d_fastcols); R->d_fastcols = nullptr;
-            TableHdr hh;
-            memset(&hh, 0, sizeof(hh));
-            hh.nslots = R->nslots;
-            hh.mask = R->nslots - 1;
-            hh.group_limit = options->group_row_limit;
-            HIP_CHECK(hipMemcpyAsync(R->d_th, &hh, sizeof(hh), hipMemcpyHostToDevice, R->stream));
-            *done = false;
-        } else {
-            R->groups_compacted = true;
-            R->groups_slim = slim != 0;
-            R->th_valid = true;
-            *done = true;
-        }
+    HIP_CHECK(R->ps.dev(&R->d_fastcols, sizeof(FastCol) * nused));
+    HIP_CHECK(hipMemcpyAsync(R->d_fastcols, fc.data(), sizeof(FastCol) * nused,
+                             hipMemcpyHostToDevice, R->stream));
+    HIP_CHECK(R->ps.dev(&R->d_cursors, sizeof(uint64_t) * kNB * nsub));
+    HIP_CHECK(hipMemsetAsync(R->d_cursors, 0, sizeof(uint64_t) * kNB * nsub, R->stream));
+    HIP_CHECK(R->ps.dev(&R->d_recs,
+                         (size_t)kNB * nsub * pp.bucket_stride * (pp.packed_mode ? 8 : 16)));
+    if (pp.has_val_nulls) {
+        HIP_CHECK(R->ps.dev(&R->d_ncursors, sizeof(uint64_t) * kNB * 8));
+        HIP_CHECK(hipMemsetAsync(R->d_ncursors, 0, sizeof(uint64_t) * kNB * 8, R->stream));
+        HIP_CHECK(R->ps.dev(&R->d_nrecs, (size_t)kNB * 8 * pp.nbucket_stride * 8));
     }
-    (void)hipEventDestroy(ev0);
-    (void)hipEventDestroy(ev1);
-    (void)hipEventDestroy(ev2);
+    /* the partitioned path's in-table sentinel is INT64_MIN bits */
+    uint64_t sk = kEmptyKey;
+    HIP_CHECK(hipMemcpyAsync((char*)R->d_th + offsetof(TableHdr, side_key_bits),
+                             &sk, 8, hipMemcpyHostToDevice, R->stream));
+
+    int64_t cap_groups = (int64_t)kNB * kHSlots;
+    if (options->max_groups_hint > 0) {
+        int64_t want = options->max_groups_hint * 2 + 4096;
+        if (want < cap_groups) cap_groups = want;
+    }
+    if (cap_groups > rows + 16) cap_groups = rows + 16;
+    R->groups_capacity = cap_groups;
+    const int slim = R->want_slim ? 1 : 0;
+    HIP_CHECK(R->ps.dev(&R->d_groups,
+                         (slim ? sizeof(SlimGroup) : sizeof(OutGroup)) * cap_groups));
+    if (!R->h_th) HIP_CHECK(R->ps.host(&R->h_th, sizeof(TableHdr)));
+    R->th_valid = false;
+    HIP_CHECK(R->ps.dev(&R->d_counter, sizeof(unsigned long long)));
+    HIP_CHECK(hipMemsetAsync(R->d_counter, 0, sizeof(unsigned long long), R->stream));
+
+    HIP_CHECK(ps.event(&ev0));
+    HIP_CHECK(ps.event(&ev1));
+    HIP_CHECK(ps.event(&ev2));
+    HIP_CHECK(hipEventRecord(ev0, R->stream));
+    HIP_CHECK(ytql_launch_scan_partition(&pp, R->d_segs, R->d_segex, R->d_fastcols,
+                                         R->d_th, R->d_cursors, R->d_recs,
+                                         R->d_ncursors, R->d_nrecs,
+                                         grid, R->stream));
+    HIP_CHECK(hipEventRecord(ev1, R->stream));
+    if (pp.direct_mode) {
+        HIP_CHECK(ytql_launch_bucket_agg_direct(R->d_recs, R->d_cursors, pp.bucket_stride,
+                                         R->d_nrecs, R->d_ncursors, pp.nbucket_stride,
+                                         R->d_groups, R->d_counter, cap_groups, slim,
+                                         R->d_th, pp.sum_slot, pp.agg_count,
+                                         pp.packed_mode, pp.bits_k,
+                                         pp.gmin_k, pp.gmin_v, pp.dshift, nsub, R->stream));
+    } else {
+        HIP_CHECK(ytql_launch_bucket_agg(R->d_recs, R->d_cursors, pp.bucket_stride,
+                                         R->d_nrecs, R->d_ncursors, pp.nbucket_stride,
+                                         R->d_groups, R->d_counter, cap_groups, slim,
+                                         R->d_th, pp.sum_slot, pp.agg_count,
+                                         pp.packed_mode, pp.bits_k,
+                                         pp.gmin_k, pp.gmin_v, nsub, R->stream));
+    }
+    HIP_CHECK(hipEventRecord(ev2, R->stream));
+    /* the header rides the synchronisation that the events need anyway */
+    HIP_CHECK(hipMemcpyAsync(R->h_th, R->d_th, sizeof(TableHdr),
+                             hipMemcpyDeviceToHost, R->stream));
+    HIP_CHECK(hipStreamSynchronize(R->stream));
+    float msA = 0, msB = 0;
+    HIP_CHECK(hipEventElapsedTime(&msA, ev0, ev1));
+    HIP_CHECK(hipEventElapsedTime(&msB, ev1, ev2));
+    if (stats) {
+        stats->kernel_scan_ms += msA;
+        stats->kernel_scan_launches += 1;
+        stats->kernel_other_ms += msB;
+    }
+    /* overflow==1 → capacity guard; retry on the direct path */
+    if (R->h_th->overflow == 1) {
+        /* reset and fall back */
+        R->ps.release(R->d_groups); R->d_groups = nullptr;
+        R->ps.release(R->d_counter); R->d_counter = nullptr;
+        R->ps.release(R->d_recs); R->d_recs = nullptr;
+        R->ps.release(R->d_cursors); R->d_cursors = nullptr;
+        R->ps.release(R->d_nrecs); R->d_nrecs = nullptr;
+        R->ps.release(R->d_ncursors); R->d_ncursors = nullptr;
+        R->ps.release(R->d_fastcols); R->d_fastcols = nullptr;
+        TableHdr hh;
+        memset(&hh, 0, sizeof(hh));
+        hh.nslots = R->nslots;
+        hh.mask = R->nslots - 1;
+        hh.group_limit = options->group_row_limit;
+        HIP_CHECK(hipMemcpyAsync(R->d_th, &hh, sizeof(hh), hipMemcpyHostToDevice, R->stream));
+        *done = false;
+    } else {
+        R->groups_compacted = true;
+        R->groups_slim = slim != 0;
+        R->th_valid = true;
+        *done = true;
+    }
     return YT_OK;
-fail:
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (ev2) (void)hipEventDestroy(ev2);
-    return rc;
 }
 
 /* run the scan (fast when possible), leaving results in the table/gaccum.
@@ -1659,6 +1680,7 @@ static int run_scan(const YtPlan* plan, const YtChunk* chunk,
                     YtStatistics* stats, char* errbuf, size_t errlen)
 {
     int rc = YT_OK;
+    PoolScope ps;                   /* the events; the blocks are R's */
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool partitioned = false;
 
@@ -1686,10 +1708,10 @@ static int run_scan(const YtPlan* plan, const YtChunk* chunk,
     rc = ensure_slots(R, plan->agg_count, errbuf, errlen);
     if (rc != YT_OK) return rc;
 
-    HIP_CHECK(hipEventCreate(&ev0));
-    HIP_CHECK(hipEventCreate(&ev1));
+    HIP_CHECK(ps.event(&ev0));
+    HIP_CHECK(ps.event(&ev1));
 
-    HIP_CHECK(pool_alloc(&R->d_gaccum, sizeof(uint64_t) * (1 + 2 * kMaxAggs)));
+    HIP_CHECK(R->ps.dev(&R->d_gaccum, sizeof(uint64_t) * (1 + 2 * kMaxAggs)));
     HIP_CHECK(hipMemsetAsync(R->d_gaccum, 0, sizeof(uint64_t) * (1 + 2 * kMaxAggs), R->stream));
 
     if (fs->valid) {
@@ -1745,7 +1767,7 @@ static int run_scan(const YtPlan* plan, const YtChunk* chunk,
             fc[u].seg_off = R->h_off[used[u]];
             fc[u].seg_cnt = R->h_cnt[used[u]];
         }
-        HIP_CHECK(pool_alloc(&R->d_fastcols, sizeof(FastCol) * nused));
+        HIP_CHECK(R->ps.dev(&R->d_fastcols, sizeof(FastCol) * nused));
         HIP_CHECK(hipMemcpyAsync(R->d_fastcols, fc.data(), sizeof(FastCol) * nused,
                                  hipMemcpyHostToDevice, R->stream));
 
@@ -1779,17 +1801,10 @@ static int run_scan(const YtPlan* plan, const YtChunk* chunk,
         HIP_CHECK(hipMemcpy(&kerr, R->d_err, sizeof(unsigned), hipMemcpyDeviceToHost));
         if (kerr) {
             set_err(errbuf, errlen, kerr == YT_ERR_DIV_ZERO ? "Division by zero" : "expression error");
-            rc = (int)kerr;
-            goto fail;
+            return (int)kerr;
         }
     }
-    (void)hipEventDestroy(ev0);
-    (void)hipEventDestroy(ev1);
     return YT_OK;
-fail:
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    return rc;
 }
 
 static inline int64_t h_zz_dec(uint64_t z)
@@ -2080,9 +2095,9 @@ static int emit_rows(const YtPlan* plan, const YtChunk* chunk,
                                             (ngroups + 131071) / 131072);
             if (nt > 32) nt = 32;
             if (nt < 1) nt = 1;
-            std::vector<std::thread> ths;
+            ThreadJoiner tj;
             for (int t = 0; t < nt; t++) {
-                ths.emplace_back([&, t]() {
+                tj.ths.emplace_back([&, t]() {
                     int64_t lo = ngroups * t / nt, hi = ngroups * (t + 1) / nt;
                     if (slim) {
                         /* slice by slice behind the copy: rows [lo, hi) */
@@ -2113,7 +2128,7 @@ static int emit_rows(const YtPlan* plan, const YtChunk* chunk,
                     }
                 });
             }
-            for (auto& t : ths) t.join();
+            tj.join();
             if (arc.load() != YT_OK) return arc.load();
             output->row_count = ngroups;
         } else if (slim) {
@@ -2275,14 +2290,6 @@ struct JoinRun {
     long long* d_fnext = nullptr;
 
     JoinRun() { memset(&jd, 0, sizeof(jd)); }
-    ~JoinRun()
-    {
-        g_pool.put(d_hkey);
-        g_pool.put(d_hrow);
-        g_pool.put(d_misc);
-        g_pool.put(d_chead);
-        g_pool.put(d_fnext);
-    }
 };
 
 /* one join item: the primary side is the row AS EXTENDED SO FAR
@@ -2332,11 +2339,11 @@ static int setup_join_item(const YtJoin* J, const uint8_t* row_types,
     JoinDev& jd = JR->jd;
     unsigned long long nr1 = 0;
     unsigned kerr = 0;
-    HIP_CHECK(pool_alloc(&JR->d_hkey, sizeof(uint64_t) * cap));
-    HIP_CHECK(pool_alloc(&JR->d_hrow, sizeof(long long) * cap));
-    HIP_CHECK(pool_alloc(&JR->d_misc, sizeof(unsigned long long) * 2));
-    HIP_CHECK(pool_alloc(&JR->d_chead, sizeof(long long) * cap));
-    HIP_CHECK(pool_alloc(&JR->d_fnext, sizeof(long long) * (fn ? fn : 1)));
+    HIP_CHECK(JR->Rf.ps.dev(&JR->d_hkey, sizeof(uint64_t) * cap));
+    HIP_CHECK(JR->Rf.ps.dev(&JR->d_hrow, sizeof(long long) * cap));
+    HIP_CHECK(JR->Rf.ps.dev(&JR->d_misc, sizeof(unsigned long long) * 2));
+    HIP_CHECK(JR->Rf.ps.dev(&JR->d_chead, sizeof(long long) * cap));
+    HIP_CHECK(JR->Rf.ps.dev(&JR->d_fnext, sizeof(long long) * (fn ? fn : 1)));
     HIP_CHECK(hipMemsetAsync(JR->d_hrow, 0xFF, sizeof(long long) * cap, stream));
     HIP_CHECK(hipMemsetAsync(JR->d_chead, 0xFF, sizeof(long long) * cap, stream));
     HIP_CHECK(hipMemsetAsync(JR->d_fnext, 0xFF, sizeof(long long) * (fn ? fn : 1), stream));
@@ -2388,8 +2395,6 @@ static int setup_join_item(const YtJoin* J, const uint8_t* row_types,
         HIP_CHECK(hipMemsetAsync(JR->Rf.d_err, 0, sizeof(unsigned), stream));
     }
     return YT_OK;
-fail:
-    return rc;
 }
 
 
@@ -2606,6 +2611,7 @@ static int run_scan_topk(const YtPlan* plan, const YtChunk* chunk,
     }
 
     DeviceRun R2;
+    PoolScope ps;
     DevPlan dpl = *dp;      /* + this run's string-predicate bitmaps */
     R2.stream = (hipStream_t)(uintptr_t)options->stream;
     unsigned mw = 0;
@@ -2657,397 +2663,370 @@ static int run_scan_topk(const YtPlan* plan, const YtChunk* chunk,
         }
     }
 
-    {
-        unsigned long long* d_bins = nullptr;   /* 2048 bins + misc(3) + ctrs(3) */
-        HIP_CHECK(pool_alloc(&d_bins, sizeof(unsigned long long) * (2048 + 8)));
-        unsigned long long* d_misc = d_bins + 2048;   /* null_cnt, mmin, mmax */
-        unsigned long long* d_ctrs = d_bins + 2051;   /* strict, tie, null */
-        HIP_CHECK(hipMemsetAsync(R2.d_err, 0, sizeof(unsigned), R2.stream));
+    unsigned long long* d_bins = nullptr;   /* 2048 bins + misc(3) + ctrs(3) */
+    HIP_CHECK(ps.dev(&d_bins, sizeof(unsigned long long) * (2048 + 8)));
+    unsigned long long* d_misc = d_bins + 2048;   /* null_cnt, mmin, mmax */
+    unsigned long long* d_ctrs = d_bins + 2051;   /* strict, tie, null */
+    HIP_CHECK(hipMemsetAsync(R2.d_err, 0, sizeof(unsigned), R2.stream));
 
-        hipEvent_t e0, e1;
-        HIP_CHECK(hipEventCreate(&e0));
-        HIP_CHECK(hipEventCreate(&e1));
-        HIP_CHECK(hipEventRecord(e0, R2.stream));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIP_CHECK(ps.event(&e0));
+    HIP_CHECK(ps.event(&e1));
+    HIP_CHECK(hipEventRecord(e0, R2.stream));
 
-        TopkPass tp;
-        tp.order_proj = ord0;
-        tp.desc = desc0;
-        tp.level0 = 1;
-        tp.shift = 53;
-        tp.lo = 0;
-        tp.hi = ~0ULL;
+    TopkPass tp;
+    tp.order_proj = ord0;
+    tp.desc = desc0;
+    tp.level0 = 1;
+    tp.shift = 53;
+    tp.lo = 0;
+    tp.hi = ~0ULL;
 
-        uint64_t lo = 0, hi = ~0ULL;
-        int shift = 53;
-        int64_t S = 0, T = 0, nonnull = 0, k_nonnull = 0;
-        unsigned long long null_cnt = 0;
-        bool all_nonnull = false, only_nulls = false;
-        std::vector<unsigned long long> h_bins(2051);
-        int launches = 0;
+    uint64_t lo = 0, hi = ~0ULL;
+    int shift = 53;
+    int64_t S = 0, T = 0, nonnull = 0, k_nonnull = 0;
+    unsigned long long null_cnt = 0;
+    bool all_nonnull = false, only_nulls = false;
+    std::vector<unsigned long long> h_bins(2051);
+    int launches = 0;
 
-        for (;;) {
-            HIP_CHECK(hipMemsetAsync(d_bins, 0,
-                                     sizeof(unsigned long long) * 2049, R2.stream));
-            if (tp.level0) {
-                /* mmin = ~0, mmax = 0 */
-                HIP_CHECK(hipMemsetAsync(d_misc + 1, 0xFF,
-                                         sizeof(unsigned long long), R2.stream));
-                HIP_CHECK(hipMemsetAsync(d_misc + 2, 0,
-                                         sizeof(unsigned long long), R2.stream));
-            }
-            if (fast_col >= 0) {
-                HIP_CHECK(ytql_launch_topk_hist_fast(
-                    R2.d_segs, R2.d_segex, R2.h_off[fast_col], fast_shift, n,
-                    fast_nulls, fast_signed, &tp, d_bins, d_misc, R2.stream));
-            } else {
-                HIP_CHECK(ytql_launch_topk_hist(dp, R2.d_segs, R2.d_segex,
-                                                R2.d_off, R2.d_cnt, n, jd,
-                                                jd2, &tp,
-                                                d_bins, d_misc,
-                                                R2.d_err, R2.stream));
-            }
-            launches++;
-            HIP_CHECK(hipMemcpy(h_bins.data(), d_bins,
-                                sizeof(unsigned long long) * 2051,
-                                hipMemcpyDeviceToHost));
-            unsigned kerr = 0;
-            HIP_CHECK(hipMemcpy(&kerr, R2.d_err, sizeof(unsigned),
-                                hipMemcpyDeviceToHost));
-            if (kerr) {
-                g_pool.put(d_bins);
-                if (kerr == 100) {
-                    set_err(errbuf, errlen, "NaN in ORDER BY comparison");
-                    return YT_ERR_LIMIT;
-                }
-                set_err(errbuf, errlen, "unsupported ORDER BY key type");
-                return (int)kerr;
-            }
-            uint64_t mmin = h_bins[2049], mmax = h_bins[2050];
-            if (tp.level0) {
-                null_cnt = h_bins[2048];
-                nonnull = 0;
-                for (int i = 0; i < 2048; i++) nonnull += (int64_t)h_bins[i];
-                const bool nulls_first = !desc0;
-                int64_t null_take = nulls_first
-                    ? ((int64_t)null_cnt < K ? (int64_t)null_cnt : K)
-                    : (K - nonnull > 0 ? K - nonnull : 0);
-                k_nonnull = K - (nulls_first ? null_take : 0);
-                if (!nulls_first && k_nonnull > nonnull) k_nonnull = nonnull;
-                if (k_nonnull <= 0) { only_nulls = true; break; }
-                if (k_nonnull >= nonnull) { all_nonnull = true; S = nonnull; break; }
-            }
-            int64_t cum = 0;
-            int t = -1;
-            for (int i = 0; i < 2048; i++) {
-                if (S + cum + (int64_t)h_bins[i] >= k_nonnull) { t = i; break; }
-                cum += (int64_t)h_bins[i];
-            }
-            if (t < 0) {   /* cannot happen: counts shrank between passes */
-                g_pool.put(d_bins);
-                set_err(errbuf, errlen, "ORDER BY selection internal error");
-                return YT_ERR_HIP;
-            }
-            S += cum;
-            T = (int64_t)h_bins[t];
-            /* shrink [lo, hi] to the chosen bin (∩ data bounds on pass 0) */
-            uint64_t nlo = lo + ((uint64_t)t << shift);
-            uint64_t span = (uint64_t)(t + 1) << shift;
-            uint64_t nhi = (span == 0 || nlo + (span - ((uint64_t)t << shift)) - 1 < nlo)
-                ? hi : nlo + (((uint64_t)1 << shift) - 1);
-            if (nhi > hi) nhi = hi;
-            if (tp.level0) {
-                if (mmin > nlo) nlo = mmin;
-                if (mmax < nhi) nhi = mmax;
-            }
-            lo = nlo;
-            hi = nhi;
-            if (T <= CAPB || shift == 0 || lo >= hi) break;
-            uint64_t range = hi - lo;     /* >= 1 */
-            shift = 0;
-            while ((range >> shift) >= 2048) shift++;
-            tp.lo = lo;
-            tp.hi = hi;
-            tp.shift = shift;
-            tp.level0 = 0;
+    for (;;) {
+        HIP_CHECK(hipMemsetAsync(d_bins, 0,
+                                 sizeof(unsigned long long) * 2049, R2.stream));
+        if (tp.level0) {
+            /* mmin = ~0, mmax = 0 */
+            HIP_CHECK(hipMemsetAsync(d_misc + 1, 0xFF,
+                                     sizeof(unsigned long long), R2.stream));
+            HIP_CHECK(hipMemsetAsync(d_misc + 2, 0,
+                                     sizeof(unsigned long long), R2.stream));
         }
-
-        if (!all_nonnull && !only_nulls && T > CAPB && plan->order_count > 1) {
-            g_pool.put(d_bins);
-            set_err(errbuf, errlen,
-                    "order-key tie set too large for multi-key ORDER BY this round");
-            return YT_ERR_UNSUPPORTED;
-        }
-        const int64_t CAPN = K + CAPB;
-        {
-            const bool nulls_first = !desc0;
-            int64_t null_take = nulls_first
-                ? ((int64_t)null_cnt < K ? (int64_t)null_cnt : K)
-                : (K - nonnull > 0 ? K - nonnull : 0);
-            if ((int64_t)null_cnt > CAPN && plan->order_count > 1 &&
-                null_take > 0 && null_take < (int64_t)null_cnt) {
-                g_pool.put(d_bins);
-                set_err(errbuf, errlen,
-                        "null order-key set too large for multi-key ORDER BY this round");
-                return YT_ERR_UNSUPPORTED;
-            }
-        }
-
-        /* gather candidates: strict (exactly S), ties (cap), nulls (cap) */
-        TopkGather tg;
-        tg.order_proj = ord0;
-        tg.desc = desc0;
-        tg.all_nonnull = all_nonnull ? 1 : 0;
-        tg.pad_ = 0;
-        /* only_nulls: nothing strict (strict is m < lo, so lo = 0 matches
-         * no row — a mapped key CAN be 0, e.g. INT64_MIN ascending, and the
-         * strict buffer is unbounded) and at most the capped tie bucket */
-        tg.lo = only_nulls ? 0 : lo;
-        tg.hi = only_nulls ? 0 : hi;
-        tg.cap_tie = CAPB;
-        tg.cap_null = CAPN;
-        int64_t* d_rows_strict = nullptr;
-        int64_t* d_rows_tie = nullptr;
-        int64_t* d_rows_null = nullptr;
-        HIP_CHECK(pool_alloc(&d_rows_strict, sizeof(int64_t) * (S ? S : 1)));
-        HIP_CHECK(pool_alloc(&d_rows_tie, sizeof(int64_t) * CAPB));
-        HIP_CHECK(pool_alloc(&d_rows_null, sizeof(int64_t) * CAPN));
-        HIP_CHECK(hipMemsetAsync(d_ctrs, 0, 3 * sizeof(unsigned long long),
-                                 R2.stream));
         if (fast_col >= 0) {
-            HIP_CHECK(ytql_launch_topk_gather_fast(
+            HIP_CHECK(ytql_launch_topk_hist_fast(
                 R2.d_segs, R2.d_segex, R2.h_off[fast_col], fast_shift, n,
-                fast_nulls, fast_signed, &tg,
-                d_rows_strict, d_ctrs, d_rows_tie, d_ctrs + 1,
-                d_rows_null, d_ctrs + 2, R2.stream));
+                fast_nulls, fast_signed, &tp, d_bins, d_misc, R2.stream));
         } else {
-            HIP_CHECK(ytql_launch_topk_gather(dp, R2.d_segs, R2.d_segex,
-                                              R2.d_off, R2.d_cnt, n, jd,
-                                              jd2, &tg,
-                                              d_rows_strict, d_ctrs,
-                                              d_rows_tie, d_ctrs + 1,
-                                              d_rows_null, d_ctrs + 2,
-                                              R2.d_err, R2.stream));
+            HIP_CHECK(ytql_launch_topk_hist(dp, R2.d_segs, R2.d_segex,
+                                            R2.d_off, R2.d_cnt, n, jd,
+                                            jd2, &tp,
+                                            d_bins, d_misc,
+                                            R2.d_err, R2.stream));
         }
         launches++;
-        unsigned long long hctrs[3];
-        HIP_CHECK(hipMemcpy(hctrs, d_ctrs, 3 * sizeof(unsigned long long),
+        HIP_CHECK(hipMemcpy(h_bins.data(), d_bins,
+                            sizeof(unsigned long long) * 2051,
                             hipMemcpyDeviceToHost));
-        int64_t nS = (int64_t)hctrs[0];
-        int64_t nB = (int64_t)hctrs[1] < CAPB ? (int64_t)hctrs[1] : CAPB;
-        int64_t nN = (int64_t)hctrs[2] < CAPN ? (int64_t)hctrs[2] : CAPN;
-        int64_t M = nS + nB + nN;
-
-        /* pack the three lists and materialize the projected rows */
-        int64_t* d_rows_all = nullptr;
-        DevOutVal* d_vals = nullptr;
-        DevOutVal* h_vals = nullptr;
-        HIP_CHECK(pool_alloc(&d_rows_all, sizeof(int64_t) * (M ? M : 1)));
-        if (nS) HIP_CHECK(hipMemcpyAsync(d_rows_all, d_rows_strict,
-                                         sizeof(int64_t) * nS,
-                                         hipMemcpyDeviceToDevice, R2.stream));
-        if (nB) HIP_CHECK(hipMemcpyAsync(d_rows_all + nS, d_rows_tie,
-                                         sizeof(int64_t) * nB,
-                                         hipMemcpyDeviceToDevice, R2.stream));
-        if (nN) HIP_CHECK(hipMemcpyAsync(d_rows_all + nS + nB, d_rows_null,
-                                         sizeof(int64_t) * nN,
-                                         hipMemcpyDeviceToDevice, R2.stream));
-        HIP_CHECK(pool_alloc(&d_vals, sizeof(DevOutVal) * (M ? M : 1) * np));
-        HIP_CHECK(pool_alloc_host(&h_vals, sizeof(DevOutVal) * (M ? M : 1) * np));
-        if (M) {
-            HIP_CHECK(ytql_launch_topk_materialize(dp, R2.d_segs, R2.d_segex,
-                                                   R2.d_off, R2.d_cnt, jd, jd2,
-                                                   d_rows_all, M, d_vals,
-                                                   R2.d_err, R2.stream));
-            launches++;
-            HIP_CHECK(hipMemcpyAsync(h_vals, d_vals, sizeof(DevOutVal) * M * np,
-                                     hipMemcpyDeviceToHost, R2.stream));
-        }
-        HIP_CHECK(hipEventRecord(e1, R2.stream));
-        HIP_CHECK(hipStreamSynchronize(R2.stream));
-        if (stats) stats->kernel_other_ms = now_ms() - tw0;  /* pre-emit wall */
-        float ms = 0;
-        HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
         unsigned kerr = 0;
         HIP_CHECK(hipMemcpy(&kerr, R2.d_err, sizeof(unsigned),
                             hipMemcpyDeviceToHost));
-        auto put_all = [&]() {
-            g_pool.put(d_bins); g_pool.put(d_rows_strict); g_pool.put(d_rows_tie);
-            g_pool.put(d_rows_null); g_pool.put(d_rows_all); g_pool.put(d_vals);
-            g_pool.put(h_vals);
-        };
         if (kerr) {
-            put_all();
             if (kerr == 100) {
                 set_err(errbuf, errlen, "NaN in ORDER BY comparison");
                 return YT_ERR_LIMIT;
             }
-            set_err(errbuf, errlen,
-                    kerr == YT_ERR_DIV_ZERO ? "Division by zero" : "expression error");
+            set_err(errbuf, errlen, "unsupported ORDER BY key type");
             return (int)kerr;
         }
+        uint64_t mmin = h_bins[2049], mmax = h_bins[2050];
+        if (tp.level0) {
+            null_cnt = h_bins[2048];
+            nonnull = 0;
+            for (int i = 0; i < 2048; i++) nonnull += (int64_t)h_bins[i];
+            const bool nulls_first = !desc0;
+            int64_t null_take = nulls_first
+                ? ((int64_t)null_cnt < K ? (int64_t)null_cnt : K)
+                : (K - nonnull > 0 ? K - nonnull : 0);
+            k_nonnull = K - (nulls_first ? null_take : 0);
+            if (!nulls_first && k_nonnull > nonnull) k_nonnull = nonnull;
+            if (k_nonnull <= 0) { only_nulls = true; break; }
+            if (k_nonnull >= nonnull) { all_nonnull = true; S = nonnull; break; }
+        }
+        int64_t cum = 0;
+        int t = -1;
+        for (int i = 0; i < 2048; i++) {
+            if (S + cum + (int64_t)h_bins[i] >= k_nonnull) { t = i; break; }
+            cum += (int64_t)h_bins[i];
+        }
+        if (t < 0) {   /* cannot happen: counts shrank between passes */
+            set_err(errbuf, errlen, "ORDER BY selection internal error");
+            return YT_ERR_HIP;
+        }
+        S += cum;
+        T = (int64_t)h_bins[t];
+        /* shrink [lo, hi] to the chosen bin (∩ data bounds on pass 0) */
+        uint64_t nlo = lo + ((uint64_t)t << shift);
+        uint64_t span = (uint64_t)(t + 1) << shift;
+        uint64_t nhi = (span == 0 || nlo + (span - ((uint64_t)t << shift)) - 1 < nlo)
+            ? hi : nlo + (((uint64_t)1 << shift) - 1);
+        if (nhi > hi) nhi = hi;
+        if (tp.level0) {
+            if (mmin > nlo) nlo = mmin;
+            if (mmax < nhi) nhi = mmax;
+        }
+        lo = nlo;
+        hi = nhi;
+        if (T <= CAPB || shift == 0 || lo >= hi) break;
+        uint64_t range = hi - lo;     /* >= 1 */
+        shift = 0;
+        while ((range >> shift) >= 2048) shift++;
+        tp.lo = lo;
+        tp.hi = hi;
+        tp.shift = shift;
+        tp.level0 = 0;
+    }
 
-        /* host: full-comparer sort of the candidates, emit the slice */
-        std::vector<int64_t> idx((size_t)M);
-        for (int64_t i = 0; i < M; i++) idx[i] = i;
-        int nan_err = 0;
-        auto cmp_cand = [&](int64_t ia, int64_t ib) {
-            const DevOutVal* a = h_vals + ia * np;
-            const DevOutVal* b = h_vals + ib * np;
-            for (int i = 0; i < plan->order_count; i++) {
-                int c = plan->order_cols[i];
-                const DevOutVal& x = a[c];
-                const DevOutVal& y = b[c];
-                int xn = x.type == YT_VT_NULL, yn = y.type == YT_VT_NULL;
-                int r = 0;
-                if (xn || yn) {
-                    r = (xn == yn) ? 0 : (xn ? -1 : 1);
-                } else if (x.type == YT_VT_DOUBLE) {
-                    double xv, yv;
-                    memcpy(&xv, &x.bits, 8);
-                    memcpy(&yv, &y.bits, 8);
-                    if (xv != xv || yv != yv) { nan_err = 1; return false; }
-                    r = xv < yv ? -1 : (xv > yv ? 1 : 0);
-                } else if (x.type == YT_VT_INT64) {
-                    int64_t xv = (int64_t)x.bits, yv = (int64_t)y.bits;
-                    r = xv < yv ? -1 : (xv > yv ? 1 : 0);
-                } else {
-                    r = x.bits < y.bits ? -1 : (x.bits > y.bits ? 1 : 0);
-                }
-                if (plan->order_desc && plan->order_desc[i]) r = -r;
-                if (r) return r < 0;
-            }
-            return false;
-        };
-        std::sort(idx.begin(), idx.end(), cmp_cand);
-        if (nan_err) {
-            put_all();
+    if (!all_nonnull && !only_nulls && T > CAPB && plan->order_count > 1) {
+        set_err(errbuf, errlen,
+                "order-key tie set too large for multi-key ORDER BY this round");
+        return YT_ERR_UNSUPPORTED;
+    }
+    const int64_t CAPN = K + CAPB;
+    {
+        const bool nulls_first = !desc0;
+        int64_t null_take = nulls_first
+            ? ((int64_t)null_cnt < K ? (int64_t)null_cnt : K)
+            : (K - nonnull > 0 ? K - nonnull : 0);
+        if ((int64_t)null_cnt > CAPN && plan->order_count > 1 &&
+            null_take > 0 && null_take < (int64_t)null_cnt) {
+            set_err(errbuf, errlen,
+                    "null order-key set too large for multi-key ORDER BY this round");
+            return YT_ERR_UNSUPPORTED;
+        }
+    }
+
+    /* gather candidates: strict (exactly S), ties (cap), nulls (cap) */
+    TopkGather tg;
+    tg.order_proj = ord0;
+    tg.desc = desc0;
+    tg.all_nonnull = all_nonnull ? 1 : 0;
+    tg.pad_ = 0;
+    /* only_nulls: nothing strict (strict is m < lo, so lo = 0 matches
+     * no row — a mapped key CAN be 0, e.g. INT64_MIN ascending, and the
+     * strict buffer is unbounded) and at most the capped tie bucket */
+    tg.lo = only_nulls ? 0 : lo;
+    tg.hi = only_nulls ? 0 : hi;
+    tg.cap_tie = CAPB;
+    tg.cap_null = CAPN;
+    int64_t* d_rows_strict = nullptr;
+    int64_t* d_rows_tie = nullptr;
+    int64_t* d_rows_null = nullptr;
+    HIP_CHECK(ps.dev(&d_rows_strict, sizeof(int64_t) * (S ? S : 1)));
+    HIP_CHECK(ps.dev(&d_rows_tie, sizeof(int64_t) * CAPB));
+    HIP_CHECK(ps.dev(&d_rows_null, sizeof(int64_t) * CAPN));
+    HIP_CHECK(hipMemsetAsync(d_ctrs, 0, 3 * sizeof(unsigned long long),
+                             R2.stream));
+    if (fast_col >= 0) {
+        HIP_CHECK(ytql_launch_topk_gather_fast(
+            R2.d_segs, R2.d_segex, R2.h_off[fast_col], fast_shift, n,
+            fast_nulls, fast_signed, &tg,
+            d_rows_strict, d_ctrs, d_rows_tie, d_ctrs + 1,
+            d_rows_null, d_ctrs + 2, R2.stream));
+    } else {
+        HIP_CHECK(ytql_launch_topk_gather(dp, R2.d_segs, R2.d_segex,
+                                          R2.d_off, R2.d_cnt, n, jd,
+                                          jd2, &tg,
+                                          d_rows_strict, d_ctrs,
+                                          d_rows_tie, d_ctrs + 1,
+                                          d_rows_null, d_ctrs + 2,
+                                          R2.d_err, R2.stream));
+    }
+    launches++;
+    unsigned long long hctrs[3];
+    HIP_CHECK(hipMemcpy(hctrs, d_ctrs, 3 * sizeof(unsigned long long),
+                        hipMemcpyDeviceToHost));
+    int64_t nS = (int64_t)hctrs[0];
+    int64_t nB = (int64_t)hctrs[1] < CAPB ? (int64_t)hctrs[1] : CAPB;
+    int64_t nN = (int64_t)hctrs[2] < CAPN ? (int64_t)hctrs[2] : CAPN;
+    int64_t M = nS + nB + nN;
+
+    /* pack the three lists and materialize the projected rows */
+    int64_t* d_rows_all = nullptr;
+    DevOutVal* d_vals = nullptr;
+    DevOutVal* h_vals = nullptr;
+    HIP_CHECK(ps.dev(&d_rows_all, sizeof(int64_t) * (M ? M : 1)));
+    if (nS) HIP_CHECK(hipMemcpyAsync(d_rows_all, d_rows_strict,
+                                     sizeof(int64_t) * nS,
+                                     hipMemcpyDeviceToDevice, R2.stream));
+    if (nB) HIP_CHECK(hipMemcpyAsync(d_rows_all + nS, d_rows_tie,
+                                     sizeof(int64_t) * nB,
+                                     hipMemcpyDeviceToDevice, R2.stream));
+    if (nN) HIP_CHECK(hipMemcpyAsync(d_rows_all + nS + nB, d_rows_null,
+                                     sizeof(int64_t) * nN,
+                                     hipMemcpyDeviceToDevice, R2.stream));
+    HIP_CHECK(ps.dev(&d_vals, sizeof(DevOutVal) * (M ? M : 1) * np));
+    HIP_CHECK(ps.host(&h_vals, sizeof(DevOutVal) * (M ? M : 1) * np));
+    if (M) {
+        HIP_CHECK(ytql_launch_topk_materialize(dp, R2.d_segs, R2.d_segex,
+                                               R2.d_off, R2.d_cnt, jd, jd2,
+                                               d_rows_all, M, d_vals,
+                                               R2.d_err, R2.stream));
+        launches++;
+        HIP_CHECK(hipMemcpyAsync(h_vals, d_vals, sizeof(DevOutVal) * M * np,
+                                 hipMemcpyDeviceToHost, R2.stream));
+    }
+    HIP_CHECK(hipEventRecord(e1, R2.stream));
+    HIP_CHECK(hipStreamSynchronize(R2.stream));
+    if (stats) stats->kernel_other_ms = now_ms() - tw0;  /* pre-emit wall */
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    unsigned kerr = 0;
+    HIP_CHECK(hipMemcpy(&kerr, R2.d_err, sizeof(unsigned),
+                        hipMemcpyDeviceToHost));
+    if (kerr) {
+        if (kerr == 100) {
             set_err(errbuf, errlen, "NaN in ORDER BY comparison");
             return YT_ERR_LIMIT;
         }
-        int64_t b = plan->order_offset < M ? plan->order_offset : M;
-        int64_t e = b + plan->order_limit;
-        if (e > M) e = M;
-        int out_limited = 0;
-        char* pool_base = nullptr;
-        if (const unsigned str_mask = string_proj_mask(dp)) {
-            /* only the emitted slice needs bytes: its string values become
-             * gather records (row order of the slice), the device fills in
-             * the lengths, the host lays them out, k_str_gather copies */
-            int64_t ne = e - b;
-            if (options->output_row_limit > 0 && ne > options->output_row_limit)
-                ne = options->output_row_limit;    /* the loop below flags it */
-            if (ne > output->capacity_rows) {
-                put_all();
-                return YT_ERR_CAPACITY;
+        set_err(errbuf, errlen,
+                kerr == YT_ERR_DIV_ZERO ? "Division by zero" : "expression error");
+        return (int)kerr;
+    }
+
+    /* host: full-comparer sort of the candidates, emit the slice */
+    std::vector<int64_t> idx((size_t)M);
+    for (int64_t i = 0; i < M; i++) idx[i] = i;
+    int nan_err = 0;
+    auto cmp_cand = [&](int64_t ia, int64_t ib) {
+        const DevOutVal* a = h_vals + ia * np;
+        const DevOutVal* b = h_vals + ib * np;
+        for (int i = 0; i < plan->order_count; i++) {
+            int c = plan->order_cols[i];
+            const DevOutVal& x = a[c];
+            const DevOutVal& y = b[c];
+            int xn = x.type == YT_VT_NULL, yn = y.type == YT_VT_NULL;
+            int r = 0;
+            if (xn || yn) {
+                r = (xn == yn) ? 0 : (xn ? -1 : 1);
+            } else if (x.type == YT_VT_DOUBLE) {
+                double xv, yv;
+                memcpy(&xv, &x.bits, 8);
+                memcpy(&yv, &y.bits, 8);
+                if (xv != xv || yv != yv) { nan_err = 1; return false; }
+                r = xv < yv ? -1 : (xv > yv ? 1 : 0);
+            } else if (x.type == YT_VT_INT64) {
+                int64_t xv = (int64_t)x.bits, yv = (int64_t)y.bits;
+                r = xv < yv ? -1 : (xv > yv ? 1 : 0);
+            } else {
+                r = x.bits < y.bits ? -1 : (x.bits > y.bits ? 1 : 0);
             }
-            std::vector<StrGatherRec> recs;
-            std::vector<DevOutVal*> owner;
-            for (int64_t i = b; i < b + ne; i++)
-                for (int pj = 0; pj < np; pj++) {
-                    DevOutVal* v = h_vals + idx[i] * np + pj;
-                    if (!((str_mask >> pj) & 1) || v->type != YT_VT_STRING)
-                        continue;
-                    StrGatherRec g;
-                    g.ref = v->bits;
-                    g.dst = 0;
-                    g.len = 0;
-                    g.pad_ = 0;
-                    recs.push_back(g);
-                    owner.push_back(v);
+            if (plan->order_desc && plan->order_desc[i]) r = -r;
+            if (r) return r < 0;
+        }
+        return false;
+    };
+    std::sort(idx.begin(), idx.end(), cmp_cand);
+    if (nan_err) {
+        set_err(errbuf, errlen, "NaN in ORDER BY comparison");
+        return YT_ERR_LIMIT;
+    }
+    int64_t b = plan->order_offset < M ? plan->order_offset : M;
+    int64_t e = b + plan->order_limit;
+    if (e > M) e = M;
+    int out_limited = 0;
+    char* pool_base = nullptr;
+    if (const unsigned str_mask = string_proj_mask(dp)) {
+        /* only the emitted slice needs bytes: its string values become
+         * gather records (row order of the slice), the device fills in
+         * the lengths, the host lays them out, k_str_gather copies */
+        int64_t ne = e - b;
+        if (options->output_row_limit > 0 && ne > options->output_row_limit)
+            ne = options->output_row_limit;    /* the loop below flags it */
+        if (ne > output->capacity_rows) return YT_ERR_CAPACITY;
+        std::vector<StrGatherRec> recs;
+        std::vector<DevOutVal*> owner;
+        for (int64_t i = b; i < b + ne; i++)
+            for (int pj = 0; pj < np; pj++) {
+                DevOutVal* v = h_vals + idx[i] * np + pj;
+                if (!((str_mask >> pj) & 1) || v->type != YT_VT_STRING)
+                    continue;
+                StrGatherRec g;
+                g.ref = v->bits;
+                g.dst = 0;
+                g.len = 0;
+                g.pad_ = 0;
+                recs.push_back(g);
+                owner.push_back(v);
+            }
+        if (!recs.empty()) {
+            const int64_t nr = (int64_t)recs.size();
+            StrGatherRec* d_recs = nullptr;
+            char* d_spool = nullptr;
+            rc = YT_OK;
+            uint64_t bytes = 0;
+            hipError_t he = ps.dev(&d_recs, sizeof(StrGatherRec) * nr);
+            if (he == hipSuccess)
+                he = hipMemcpy(d_recs, recs.data(), sizeof(StrGatherRec) * nr,
+                               hipMemcpyHostToDevice);
+            if (he == hipSuccess)
+                he = ytql_launch_str_reclen(R2.d_segs, R2.d_segex, d_recs, nr,
+                                            R2.stream);
+            if (he == hipSuccess) he = hipStreamSynchronize(R2.stream);
+            if (he == hipSuccess)
+                he = hipMemcpy(recs.data(), d_recs, sizeof(StrGatherRec) * nr,
+                               hipMemcpyDeviceToHost);
+            if (he == hipSuccess) {
+                for (int64_t i = 0; i < nr; i++) {
+                    recs[i].dst = bytes;
+                    owner[i]->bits = bytes;      /* offset in this slice */
+                    owner[i]->pad_ = recs[i].len;
+                    bytes += recs[i].len;
                 }
-            if (!recs.empty()) {
-                const int64_t nr = (int64_t)recs.size();
-                StrGatherRec* d_recs = nullptr;
-                char* d_spool = nullptr;
-                rc = YT_OK;
-                uint64_t bytes = 0;
-                hipError_t he = pool_alloc(&d_recs, sizeof(StrGatherRec) * nr);
+                if (bytes > 0 &&
+                    (!output->string_pool ||
+                     (uint64_t)output->string_pool_used + bytes >
+                         (uint64_t)output->string_pool_capacity)) {
+                    set_err(errbuf, errlen, "string pool too small");
+                    rc = YT_ERR_CAPACITY;
+                }
+            }
+            if (he == hipSuccess && rc == YT_OK && bytes) {
+                pool_base = output->string_pool + output->string_pool_used;
+                he = ps.dev(&d_spool, (size_t)bytes);
                 if (he == hipSuccess)
-                    he = hipMemcpy(d_recs, recs.data(), sizeof(StrGatherRec) * nr,
+                    he = hipMemcpy(d_recs, recs.data(),
+                                   sizeof(StrGatherRec) * nr,
                                    hipMemcpyHostToDevice);
                 if (he == hipSuccess)
-                    he = ytql_launch_str_reclen(R2.d_segs, R2.d_segex, d_recs, nr,
-                                                R2.stream);
+                    he = ytql_launch_str_gather(R2.d_segs, R2.d_segex, d_recs,
+                                                nr, d_spool, bytes, R2.stream);
                 if (he == hipSuccess) he = hipStreamSynchronize(R2.stream);
                 if (he == hipSuccess)
-                    he = hipMemcpy(recs.data(), d_recs, sizeof(StrGatherRec) * nr,
+                    he = hipMemcpy(pool_base, d_spool, (size_t)bytes,
                                    hipMemcpyDeviceToHost);
-                if (he == hipSuccess) {
-                    for (int64_t i = 0; i < nr; i++) {
-                        recs[i].dst = bytes;
-                        owner[i]->bits = bytes;      /* offset in this slice */
-                        owner[i]->pad_ = recs[i].len;
-                        bytes += recs[i].len;
-                    }
-                    if (bytes > 0 &&
-                        (!output->string_pool ||
-                         (uint64_t)output->string_pool_used + bytes >
-                             (uint64_t)output->string_pool_capacity)) {
-                        set_err(errbuf, errlen, "string pool too small");
-                        rc = YT_ERR_CAPACITY;
-                    }
-                }
-                if (he == hipSuccess && rc == YT_OK && bytes) {
-                    pool_base = output->string_pool + output->string_pool_used;
-                    he = pool_alloc(&d_spool, (size_t)bytes);
-                    if (he == hipSuccess)
-                        he = hipMemcpy(d_recs, recs.data(),
-                                       sizeof(StrGatherRec) * nr,
-                                       hipMemcpyHostToDevice);
-                    if (he == hipSuccess)
-                        he = ytql_launch_str_gather(R2.d_segs, R2.d_segex, d_recs,
-                                                    nr, d_spool, bytes, R2.stream);
-                    if (he == hipSuccess) he = hipStreamSynchronize(R2.stream);
-                    if (he == hipSuccess)
-                        he = hipMemcpy(pool_base, d_spool, (size_t)bytes,
-                                       hipMemcpyDeviceToHost);
-                    launches += 2;
-                }
-                g_pool.put(d_recs);
-                g_pool.put(d_spool);
-                if (he != hipSuccess) {
-                    if (errbuf) snprintf(errbuf, errlen, "HIP error %s (string gather)",
-                                         hipGetErrorString(he));
-                    rc = YT_ERR_HIP;
-                }
-                if (rc != YT_OK) {
-                    put_all();
-                    return rc;
-                }
-                output->string_pool_used += (int64_t)bytes;
+                launches += 2;
             }
-        }
-        for (int64_t i = b; i < e; i++) {
-            if (options->output_row_limit > 0 &&
-                output->row_count >= options->output_row_limit) {
-                out_limited = 1;
-                break;
+            ps.release(d_recs);
+            ps.release(d_spool);
+            if (he != hipSuccess) {
+                if (errbuf) snprintf(errbuf, errlen, "HIP error %s (string gather)",
+                                     hipGetErrorString(he));
+                rc = YT_ERR_HIP;
             }
-            if (output->row_count >= output->capacity_rows) {
-                put_all();
-                return YT_ERR_CAPACITY;
-            }
-            const DevOutVal* src = h_vals + idx[i] * np;
-            YtValue* dst = output->values + output->row_count * np;
-            for (int pj = 0; pj < np; pj++)
-                emit_proj_value(dst + pj, pj, src[pj], pool_base);
-            output->row_count++;
+            if (rc != YT_OK) return rc;
+            output->string_pool_used += (int64_t)bytes;
         }
-        if (stats) {
-            stats->rows_read = n;
-            stats->rows_written = output->row_count;
-            stats->incomplete_output = out_limited;
-            stats->kernel_scan_ms += ms;
-            stats->kernel_scan_launches += launches;
-            stats->execute_time_ms = now_ms() - tw0;
+    }
+    for (int64_t i = b; i < e; i++) {
+        if (options->output_row_limit > 0 &&
+            output->row_count >= options->output_row_limit) {
+            out_limited = 1;
+            break;
         }
-        put_all();
+        if (output->row_count >= output->capacity_rows) return YT_ERR_CAPACITY;
+        const DevOutVal* src = h_vals + idx[i] * np;
+        YtValue* dst = output->values + output->row_count * np;
+        for (int pj = 0; pj < np; pj++)
+            emit_proj_value(dst + pj, pj, src[pj], pool_base);
+        output->row_count++;
+    }
+    if (stats) {
+        stats->rows_read = n;
+        stats->rows_written = output->row_count;
+        stats->incomplete_output = out_limited;
+        stats->kernel_scan_ms += ms;
+        stats->kernel_scan_launches += launches;
+        stats->execute_time_ms = now_ms() - tw0;
     }
     return YT_OK;
-fail:
-    return rc;
 }
 
 /* bit pj set = projection pj is one P_STR_REF (a plain STRING column) */
@@ -3090,7 +3069,6 @@ static int scan_project_compact(const YtPlan* plan, const YtExecOptions* options
                                 YtRowset* output, YtStatistics* stats, double tw0,
                                 char* errbuf, size_t errlen)
 {
-    int rc = YT_OK;
     const int np = plan->project_count;
     int nstr = 0;
     for (int pj = 0; pj < np; pj++) nstr += (str_mask >> pj) & 1;
@@ -3114,15 +3092,16 @@ static int scan_project_compact(const YtPlan* plan, const YtExecOptions* options
     float t_scan = 0, t_off = 0, t_scat = 0, t_gath = 0;
     double t_host = 0;
     int windows = 0;
+    PoolScope ps;
     auto put_win = [&]() {
-        g_pool.put(d_cout); g_pool.put(d_recs); g_pool.put(d_pool);
-        g_pool.put(h_out);
+        ps.release(d_cout); ps.release(d_recs); ps.release(d_pool);
+        ps.release(h_out);
         d_cout = nullptr; d_recs = nullptr; d_pool = nullptr; h_out = nullptr;
     };
-    HIP_CHECK(pool_alloc(&d_out, sizeof(DevOutVal) * win * np));
-    HIP_CHECK(pool_alloc(&d_pass, (size_t)win));
-    HIP_CHECK(pool_alloc(&d_tiles, sizeof(ProjTot) * (max_tiles + 1)));
-    for (int i = 0; i < 5; i++) HIP_CHECK(hipEventCreate(&ev[i]));
+    HIP_CHECK(ps.dev(&d_out, sizeof(DevOutVal) * win * np));
+    HIP_CHECK(ps.dev(&d_pass, (size_t)win));
+    HIP_CHECK(ps.dev(&d_tiles, sizeof(ProjTot) * (max_tiles + 1)));
+    for (int i = 0; i < 5; i++) HIP_CHECK(ps.event(&ev[i]));
     HIP_CHECK(hipMemsetAsync(R->d_err, 0, sizeof(unsigned), R->stream));
     for (int64_t w0 = 0; w0 < n; w0 += win) {
         const int64_t wlen = (w0 + win <= n) ? win : (n - w0);
@@ -3147,8 +3126,7 @@ static int scan_project_compact(const YtPlan* plan, const YtExecOptions* options
         HIP_CHECK(hipStreamSynchronize(R->stream));
         if (kerr) {
             set_err(errbuf, errlen, kerr == YT_ERR_DIV_ZERO ? "Division by zero" : "expression error");
-            rc = (int)kerr;
-            goto fail;
+            return (int)kerr;
         }
         const int64_t wrows = (int64_t)tot.rows;
         float ms = 0;
@@ -3169,14 +3147,13 @@ static int scan_project_compact(const YtPlan* plan, const YtExecOptions* options
         }
         if (output->row_count + take > output->capacity_rows) {
             set_err(errbuf, errlen, "rowset too small");
-            rc = YT_ERR_CAPACITY;
-            goto fail;
+            return YT_ERR_CAPACITY;
         }
         if (take > 0) {
-            HIP_CHECK(pool_alloc(&d_cout, sizeof(DevOutVal) * wrows * np));
-            HIP_CHECK(pool_alloc(&d_recs, sizeof(StrGatherRec) * wrows * nstr));
-            HIP_CHECK(pool_alloc(&d_pool, (size_t)(tot.bytes ? tot.bytes : 1)));
-            HIP_CHECK(pool_alloc_host(&h_out, sizeof(DevOutVal) * take * np));
+            HIP_CHECK(ps.dev(&d_cout, sizeof(DevOutVal) * wrows * np));
+            HIP_CHECK(ps.dev(&d_recs, sizeof(StrGatherRec) * wrows * nstr));
+            HIP_CHECK(ps.dev(&d_pool, (size_t)(tot.bytes ? tot.bytes : 1)));
+            HIP_CHECK(ps.host(&h_out, sizeof(DevOutVal) * take * np));
             HIP_CHECK(hipEventRecord(ev[2], R->stream));
             HIP_CHECK(ytql_launch_proj_scatter(d_out, d_pass, wlen, np, str_mask,
                                                nstr, d_tiles, d_cout, d_recs,
@@ -3208,8 +3185,7 @@ static int scan_project_compact(const YtPlan* plan, const YtExecOptions* options
                  (uint64_t)output->string_pool_used + bytes >
                      (uint64_t)output->string_pool_capacity)) {
                 set_err(errbuf, errlen, "string pool too small");
-                rc = YT_ERR_CAPACITY;
-                goto fail;
+                return YT_ERR_CAPACITY;
             }
             char* pool_base = output->string_pool
                 ? output->string_pool + output->string_pool_used : nullptr;
@@ -3248,12 +3224,7 @@ static int scan_project_compact(const YtPlan* plan, const YtExecOptions* options
                 windows, (long long)output->row_count,
                 (long long)output->string_pool_used, t_scan, t_off, t_scat,
                 t_gath, t_host);
-fail:
-    put_win();
-    g_pool.put(d_out); g_pool.put(d_pass); g_pool.put(d_tiles);
-    for (int i = 0; i < 5; i++)
-        if (ev[i]) (void)hipEventDestroy(ev[i]);
-    return rc;
+    return YT_OK;
 }
 
 /* scan + filter + project: order-preserving (MakeCodegenProjectOp +
@@ -3269,6 +3240,7 @@ static int run_scan_project(const YtPlan* plan, const YtChunk* chunk,
 {
     int rc = YT_OK;
     DeviceRun R2;
+    PoolScope ps;
     DevPlan dpl = *dp;      /* + this run's string-predicate bitmaps */
     R2.stream = (hipStream_t)(uintptr_t)options->stream;
     unsigned mw = 0;
@@ -3292,28 +3264,27 @@ static int run_scan_project(const YtPlan* plan, const YtChunk* chunk,
                                     output, stats, tw0, errbuf, errlen);
     }
     if (n == 0 || R2.nsegs == 0) return YT_OK;
-    {
-        /* stream the scan through bounded windows: the per-row
-         * materialization buffer is at most kWin rows, so arbitrarily
-         * large inputs need only bounded device/host memory */
-        const int64_t kWin = (int64_t)1 << 24;
-        const int64_t win = n < kWin ? n : kWin;
-        DevOutVal* d_out = nullptr;
-        uint8_t* d_pass = nullptr;
-        DevOutVal* h_out = nullptr;
-        uint8_t* h_pass = nullptr;
-        HIP_CHECK(pool_alloc(&d_out, sizeof(DevOutVal) * win * plan->project_count));
-        HIP_CHECK(pool_alloc(&d_pass, (size_t)win));
-        HIP_CHECK(pool_alloc_host(&h_out, sizeof(DevOutVal) * win * plan->project_count));
-        HIP_CHECK(pool_alloc_host(&h_pass, (size_t)win));
-        HIP_CHECK(hipMemsetAsync(R2.d_err, 0, sizeof(unsigned), R2.stream));
-        float ms = 0;
-        int np = plan->project_count;
-        for (int64_t w0 = 0; w0 < n; w0 += win) {
+    /* stream the scan through bounded windows: the per-row
+     * materialization buffer is at most kWin rows, so arbitrarily
+     * large inputs need only bounded device/host memory */
+    const int64_t kWin = (int64_t)1 << 24;
+    const int64_t win = n < kWin ? n : kWin;
+    DevOutVal* d_out = nullptr;
+    uint8_t* d_pass = nullptr;
+    DevOutVal* h_out = nullptr;
+    uint8_t* h_pass = nullptr;
+    HIP_CHECK(ps.dev(&d_out, sizeof(DevOutVal) * win * plan->project_count));
+    HIP_CHECK(ps.dev(&d_pass, (size_t)win));
+    HIP_CHECK(ps.host(&h_out, sizeof(DevOutVal) * win * plan->project_count));
+    HIP_CHECK(ps.host(&h_pass, (size_t)win));
+    HIP_CHECK(hipMemsetAsync(R2.d_err, 0, sizeof(unsigned), R2.stream));
+    float ms = 0;
+    int np = plan->project_count;
+    hipEvent_t e0 = nullptr, e1 = nullptr;      /* reused by every window */
+    HIP_CHECK(ps.event(&e0));
+    HIP_CHECK(ps.event(&e1));
+    for (int64_t w0 = 0; w0 < n; w0 += win) {
         const int64_t wlen = (w0 + win <= n) ? win : (n - w0);
-        hipEvent_t e0, e1;
-        HIP_CHECK(hipEventCreate(&e0));
-        HIP_CHECK(hipEventCreate(&e1));
         HIP_CHECK(hipEventRecord(e0, R2.stream));
         HIP_CHECK(ytql_launch_scan_project(dp, R2.d_segs, R2.d_segex, R2.d_off,
                                            R2.d_cnt, w0, wlen, jd, jd2, d_out,
@@ -3327,13 +3298,9 @@ static int run_scan_project(const YtPlan* plan, const YtChunk* chunk,
         float wms = 0;
         HIP_CHECK(hipEventElapsedTime(&wms, e0, e1));
         ms += wms;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
         unsigned kerr = 0;
         HIP_CHECK(hipMemcpy(&kerr, R2.d_err, sizeof(unsigned), hipMemcpyDeviceToHost));
         if (kerr) {
-            g_pool.put(d_out); g_pool.put(d_pass);
-            g_pool.put(h_out); g_pool.put(h_pass);
             set_err(errbuf, errlen, kerr == YT_ERR_DIV_ZERO ? "Division by zero" : "expression error");
             return (int)kerr;
         }
@@ -3344,11 +3311,7 @@ static int run_scan_project(const YtPlan* plan, const YtChunk* chunk,
                 if (stats) stats->incomplete_output = 1;
                 break;
             }
-            if (output->row_count >= output->capacity_rows) {
-                g_pool.put(d_out); g_pool.put(d_pass);
-                g_pool.put(h_out); g_pool.put(h_pass);
-                return YT_ERR_CAPACITY;
-            }
+            if (output->row_count >= output->capacity_rows) return YT_ERR_CAPACITY;
             YtValue* dst = output->values + output->row_count * np;
             for (int pj = 0; pj < np; pj++) {
                 const DevOutVal& o = h_out[r2 * np + pj];
@@ -3363,20 +3326,15 @@ static int run_scan_project(const YtPlan* plan, const YtChunk* chunk,
         if (options->output_row_limit > 0 &&
             output->row_count >= options->output_row_limit)
             break;
-        }
-        if (stats) {
-            stats->rows_read = n;
-            stats->rows_written = output->row_count;
-            stats->kernel_scan_ms += ms;
-            stats->kernel_scan_launches += 1;
-            stats->execute_time_ms = now_ms() - tw0;
-        }
-        g_pool.put(d_out); g_pool.put(d_pass);
-        g_pool.put(h_out); g_pool.put(h_pass);
+    }
+    if (stats) {
+        stats->rows_read = n;
+        stats->rows_written = output->row_count;
+        stats->kernel_scan_ms += ms;
+        stats->kernel_scan_launches += 1;
+        stats->execute_time_ms = now_ms() - tw0;
     }
     return YT_OK;
-fail:
-    return rc;
 }
 
 
@@ -3451,6 +3409,375 @@ static int emit_string_general(const YtPlan* plan, const uint8_t* sum_type,
     return YT_OK;
 }
 
+/* one [key(string), aggs...] row of the specialised {sum, sum(1)} shape; a
+ * key_type of YT_VT_NULL writes the null-key row */
+static inline void write_str_sum_row(YtValue* dst, int agg_count,
+                                     uint8_t key_type, uint32_t key_len,
+                                     const char* key, uint64_t cnt,
+                                     uint64_t nonnull, uint64_t sum_bits,
+                                     const int* agg_is_sum1, int val_is_double)
+{
+    dst[0].id = 0;
+    dst[0].type = key_type;
+    dst[0].flags = 0;
+    dst[0].length = key_len;
+    if (key_type == YT_VT_STRING) dst[0].data.str = key;
+    else dst[0].data.bits = 0;
+    for (int a = 0; a < agg_count; a++) {
+        YtValue& v = dst[1 + a];
+        v.id = (uint16_t)(1 + a);
+        v.flags = 0;
+        v.length = 0;
+        if (agg_is_sum1[a]) {
+            v.type = YT_VT_INT64;
+            v.data.bits = cnt;
+        } else if (nonnull == 0) {
+            v.type = YT_VT_NULL;
+            v.data.bits = 0;
+        } else {
+            v.type = val_is_double ? YT_VT_DOUBLE : YT_VT_INT64;
+            v.data.bits = sum_bits;
+        }
+    }
+}
+
+/* the null-key row of that shape, from the table header's side group */
+static inline void write_str_sum_null_row(YtValue* dst, int agg_count,
+                                          const TableHdr& th, int sum_slot,
+                                          const int* agg_is_sum1,
+                                          int val_is_double)
+{
+    write_str_sum_row(dst, agg_count, YT_VT_NULL, 0, nullptr, th.side_cnt[1],
+                      sum_slot >= 0 ? th.side_agg[1][2 * sum_slot + 1] : 0,
+                      sum_slot >= 0 ? th.side_agg[1][2 * sum_slot] : 0,
+                      agg_is_sum1, val_is_double);
+}
+
+/* memcpy in 64 MB pieces, one thread each */
+static void copy_parallel(char* dst, const char* src, size_t bytes)
+{
+    const int ct = (int)std::min<size_t>(std::thread::hardware_concurrency(),
+                                         (bytes + (64 << 20) - 1) / (64 << 20));
+    if (ct <= 1) {
+        if (bytes) memcpy(dst, src, bytes);
+        return;
+    }
+    ThreadJoiner cth;
+    const size_t per = (bytes + ct - 1) / ct;
+    for (int t = 0; t < ct; t++) {
+        const size_t b = (size_t)t * per;
+        const size_t e = std::min(bytes, b + per);
+        if (b >= e) break;
+        cth.ths.emplace_back([=] { memcpy(dst + b, src + b, e - b); });
+    }
+}
+
+/* what run_string_group learns from the plan and the host-visible segment
+ * meta before it touches the device */
+struct StrGroupShape {
+    bool general;
+    int sum_slot, sum_col, val_is_double;
+    uint8_t col_types[kMaxCols];
+};
+
+/* which of the two kernel sets the plan takes, and the refusals that need no
+ * device; `partial` is the bottom query (the state row carries one sum) */
+static int classify_string_group(const YtPlan* plan, const YtChunk* chunk,
+                                 int key_col, bool partial, StrGroupShape* sh,
+                                 char* errbuf, size_t errlen)
+{
+    sh->sum_slot = -1;
+    sh->sum_col = -1;
+    sh->val_is_double = 0;
+    bool general = plan->filter != nullptr;
+    memset(sh->col_types, YT_VT_INT64, sizeof(sh->col_types));
+    for (int c = 0; c < chunk->column_count && c < kMaxCols; c++)
+        sh->col_types[c] = (uint8_t)chunk->columns[c].value_type;
+    for (int a = 0; a < plan->agg_count; a++) {
+        int f = plan->aggs[a]->func;
+        if (f == YT_AGG_SUM) {
+            int c;
+            if (sh->sum_slot >= 0) {
+                if (partial) {
+                    set_err(errbuf, errlen,
+                            "partial_str: the string state row carries one sum");
+                    return YT_ERR_UNSUPPORTED;
+                }
+                general = true;
+                continue;
+            }
+            sh->sum_slot = a;
+            if (expr_is_col(plan->aggs[a]->arg, &c) && c >= 0 &&
+                c < chunk->column_count && c < kMaxCols) {
+                sh->sum_col = c;
+                sh->val_is_double = sh->col_types[c] == YT_VT_DOUBLE;
+                if (!sh->val_is_double && sh->col_types[c] != YT_VT_INT64)
+                    general = true;
+            } else {
+                general = true;     /* sum(<expression>) */
+            }
+        } else if (f != YT_AGG_SUM1) {
+            if (partial) {
+                set_err(errbuf, errlen,
+                        "partial_str: min/max/avg/first are not exchanged for "
+                        "string keys (the state row carries sum and sum(1))");
+                return YT_ERR_UNSUPPORTED;
+            }
+            general = true;
+        }
+    }
+    if (plan->project_count) {
+        set_err(errbuf, errlen, "string keys: no post-projection this round");
+        return YT_ERR_UNSUPPORTED;
+    }
+    /* key layout and segmentation decide too (host-visible segment meta) */
+    const YtColumn& kcol = chunk->columns[key_col];
+    for (int i = 0; i < kcol.segment_count; i++) {
+        if (kcol.segments[i].type == YT_SEG_DIRECT_RLE) general = true;
+        if (i + 1 < kcol.segment_count &&
+            kcol.segments[i].row_count != kcol.segments[0].row_count)
+            general = true;
+    }
+    if (!general && sh->sum_col >= 0) {
+        const YtColumn& vcol = chunk->columns[sh->sum_col];
+        if (vcol.segment_count != kcol.segment_count) general = true;
+        for (int i = 0; !general && i < kcol.segment_count; i++)
+            if (vcol.segments[i].row_count != kcol.segments[i].row_count)
+                general = true;
+    }
+    sh->general = general;
+    return YT_OK;
+}
+
+/* bottom query: hash-partition the compacted groups + the null side group
+ * into state rows and per-partition pool slices (key_bits = slice-local
+ * offset<<24 | len); *state_rows = rows written */
+static int partition_string_groups(PoolScope& ps, StrPartialOut* po,
+                                   hipStream_t stream, const OutStrGroup* d_out,
+                                   int64_t ngroups, const char* d_pool,
+                                   const TableHdr& th, int sum_slot,
+                                   int val_is_double, int64_t* state_rows,
+                                   char* errbuf, size_t errlen)
+{
+    const int np = po->partition_count;
+    const int p_null = (int)(splitmix64_host(
+        0xCBF29CE484222325ULL ^ 0xDEADBEEF12345678ULL) % (uint64_t)np);
+    unsigned long long* d_pc = nullptr;   /* [np] counts, [np] bytes,
+                                             [np] cursors, [np] bcursors,
+                                             [np] pool_base */
+    HIP_CHECK(ps.dev(&d_pc, sizeof(unsigned long long) * np * 5));
+    HIP_CHECK(hipMemsetAsync(d_pc, 0, sizeof(unsigned long long) * np * 5,
+                             stream));
+    if (ngroups > 0) {
+        HIP_CHECK(ytql_launch_strst_count(d_out, ngroups, d_pool, np,
+                                          d_pc, d_pc + np, stream));
+    }
+    std::vector<unsigned long long> pc(2 * np);
+    HIP_CHECK(hipMemcpyAsync(pc.data(), d_pc,
+                             sizeof(unsigned long long) * 2 * np,
+                             hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    if (th.side_used[1]) pc[p_null] += 1;
+    unsigned long long rrun = 0, brun = 0;
+    std::vector<unsigned long long> rcur(np), pbase(np);
+    for (int p = 0; p < np; p++) {
+        rcur[p] = rrun;
+        pbase[p] = brun;
+        rrun += pc[p];
+        brun += pc[np + p];
+    }
+    if ((int64_t)rrun > po->capacity_rows
+        || (int64_t)brun > po->pool_capacity) {
+        set_err(errbuf, errlen, "partial_str: state/pool buffer too small");
+        return YT_ERR_CAPACITY;
+    }
+    HIP_CHECK(hipMemcpyAsync(d_pc + 2 * np, rcur.data(),
+                             sizeof(unsigned long long) * np,
+                             hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemsetAsync(d_pc + 3 * np, 0,
+                             sizeof(unsigned long long) * np, stream));
+    HIP_CHECK(hipMemcpyAsync(d_pc + 4 * np, pbase.data(),
+                             sizeof(unsigned long long) * np,
+                             hipMemcpyHostToDevice, stream));
+    if (ngroups > 0) {
+        HIP_CHECK(ytql_launch_strst_scatter(d_out, ngroups, d_pool, np,
+                                            val_is_double,
+                                            d_pc + 2 * np, d_pc + 3 * np,
+                                            po->states_device, po->pool_device,
+                                            d_pc + 4 * np, stream));
+    }
+    HIP_CHECK(hipStreamSynchronize(stream));
+    if (th.side_used[1]) {
+        unsigned long long pos = 0;
+        HIP_CHECK(hipMemcpy(&pos, d_pc + 2 * np + p_null,
+                            sizeof(pos), hipMemcpyDeviceToHost));
+        YtStateRow sr;
+        memset(&sr, 0, sizeof(sr));
+        sr.key_bits = 0;
+        uint64_t nn = sum_slot >= 0 ? th.side_agg[1][2 * sum_slot + 1] : 0;
+        sr.meta = 1ULL | (val_is_double ? 2ULL : 0ULL) | (nn << 8);
+        sr.sum_bits = sum_slot >= 0 ? th.side_agg[1][2 * sum_slot] : 0;
+        sr.row_count = th.side_cnt[1];
+        HIP_CHECK(hipMemcpy(po->states_device + pos, &sr, sizeof(sr),
+                            hipMemcpyHostToDevice));
+    }
+    for (int p = 0; p < np; p++) {
+        po->part_counts[p] = (int64_t)pc[p];
+        po->part_pool_bytes[p] = (int64_t)pc[np + p];
+    }
+    *state_rows = (int64_t)rrun;
+    return YT_OK;
+}
+
+/* specialised path: emit [key(string), aggs...] rows from the compacted
+ * groups in d_out and their key bytes in d_pool (pool_bytes of them), then
+ * the null-key side group. hgroups is the pinned landing area for d_out. */
+static int emit_string_sums(PoolScope& ps, const YtPlan* plan,
+                            const YtExecOptions* options, hipStream_t stream,
+                            const OutStrGroup* d_out, OutStrGroup* hgroups,
+                            int64_t ngroups, const char* d_pool,
+                            uint64_t pool_bytes, const TableHdr& th,
+                            int sum_slot, int val_is_double, int* out_limited,
+                            YtRowset* output, char* errbuf, size_t errlen)
+{
+    const int nagg = plan->agg_count;
+    const int ncols = 1 + nagg;
+    const int has_null_row = th.side_used[1] ? 1 : 0;
+    int agg_is_sum1[kMaxAggs];
+    for (int a = 0; a < nagg; a++)
+        agg_is_sum1[a] = plan->aggs[a]->func == YT_AGG_SUM1;
+
+    /* Fast path (no output limit, everything fits): copy the device key pool
+     * wholesale — compact's pool_off values are global offsets into it — and
+     * fill the YtValue rows with host threads. */
+    if (options->output_row_limit == 0 &&
+        ngroups + has_null_row <= output->capacity_rows &&
+        pool_bytes <= (unsigned long long)output->string_pool_capacity &&
+        (output->string_pool != nullptr || pool_bytes == 0)) {
+        /* pipeline: pool D2H first, then hgroups in slices — the
+         * parallel host copies/emits of slice s overlap slice s+1's
+         * D2H (the serial tail was D2H then copy then emit) */
+        char* stage = nullptr;
+        if (pool_bytes) {
+            HIP_CHECK(ps.host(&stage, pool_bytes));
+            HIP_CHECK(hipMemcpyAsync(stage, d_pool, pool_bytes,
+                                     hipMemcpyDeviceToHost, stream));
+        }
+        const int kSlices = (ngroups >= (1 << 21)) ? 8 : 1;
+        std::vector<hipEvent_t> sl_ev(kSlices, nullptr);
+        const int64_t per_sl = (ngroups + kSlices - 1) / kSlices;
+        for (int s2 = 0; s2 < kSlices; s2++) {
+            int64_t b = (int64_t)s2 * per_sl;
+            int64_t e = std::min<int64_t>(ngroups, b + per_sl);
+            if (b >= e) break;
+            HIP_CHECK(hipMemcpyAsync(hgroups + b, d_out + b,
+                                     sizeof(OutStrGroup) * (e - b),
+                                     hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(ps.event(&sl_ev[s2]));
+            HIP_CHECK(hipEventRecord(sl_ev[s2], stream));
+        }
+        ThreadJoiner tj;        /* before the checks that run beside threads */
+        if (pool_bytes) {
+            /* pool D2H was queued first — wait for the FIRST slice event
+             * (>= pool completion), then copy to the caller's pool off
+             * the critical path */
+            hipEvent_t after_pool = sl_ev[0];
+            if (!after_pool) {
+                HIP_CHECK(hipStreamSynchronize(stream));
+            }
+            const size_t total_b = (size_t)pool_bytes;
+            char* dst_pool = output->string_pool;
+            tj.ths.emplace_back([stage, dst_pool, total_b, after_pool] {
+                if (after_pool) (void)hipEventSynchronize(after_pool);
+                copy_parallel(dst_pool, stage, total_b);
+            });
+        }
+        output->string_pool_used = pool_bytes;
+        auto emit_range = [&](int64_t b, int64_t e) {
+            for (int64_t gI = b; gI < e; gI++) {
+                const OutStrGroup& g = hgroups[gI];
+                write_str_sum_row(output->values + gI * ncols, nagg,
+                                  YT_VT_STRING, (uint32_t)(g.off_len & 0xFFFFFF),
+                                  output->string_pool + (g.off_len >> 24),
+                                  g.cnt_nonnull & 0xFFFFFFFFULL,
+                                  g.cnt_nonnull >> 32, g.sum_bits,
+                                  agg_is_sum1, val_is_double);
+            }
+        };
+        int nt = (int)std::thread::hardware_concurrency();
+        if (nt < 1) nt = 1;
+        if (nt > 64) nt = 64;
+        if (ngroups < (1 << 16)) nt = 1;
+        for (int s2 = 0; s2 < kSlices; s2++) {
+            int64_t sb = (int64_t)s2 * per_sl;
+            int64_t se = std::min<int64_t>(ngroups, sb + per_sl);
+            if (sb >= se) break;
+            if (sl_ev[s2]) HIP_CHECK(hipEventSynchronize(sl_ev[s2]));
+            if (nt == 1) {
+                emit_range(sb, se);
+                continue;
+            }
+            int kt = nt / kSlices > 0 ? nt / kSlices : 1;
+            int64_t per = (se - sb + kt - 1) / kt;
+            for (int t = 0; t < kt; t++) {
+                int64_t b = sb + (int64_t)t * per, e = b + per;
+                if (b >= se) break;
+                if (e > se) e = se;
+                tj.ths.emplace_back(emit_range, b, e);
+            }
+        }
+        tj.join();
+        output->row_count = ngroups;
+        if (has_null_row) {
+            write_str_sum_null_row(output->values + output->row_count * ncols,
+                                   nagg, th, sum_slot, agg_is_sum1, val_is_double);
+            output->row_count++;
+        }
+        return YT_OK;
+    }
+
+    /* limited path: output_row_limit, or a rowset or pool that may be too
+     * small — one copy each of the pool and the groups, rows one by one */
+    std::vector<char> pool(pool_bytes ? pool_bytes : 1);
+    if (pool_bytes) {
+        HIP_CHECK(hipMemcpy(pool.data(), d_pool, pool_bytes, hipMemcpyDeviceToHost));
+    }
+    if (ngroups > 0) {
+        HIP_CHECK(hipMemcpy(hgroups, d_out, sizeof(OutStrGroup) * ngroups,
+                            hipMemcpyDeviceToHost));
+    }
+    for (int64_t gI = 0; gI < ngroups + 1; gI++) {
+        const int knull = gI == ngroups;
+        if (knull && !has_null_row) break;
+        if (options->output_row_limit > 0 &&
+            output->row_count >= options->output_row_limit) {
+            *out_limited = 1;
+            break;
+        }
+        if (output->row_count >= output->capacity_rows) return YT_ERR_CAPACITY;
+        YtValue* dst = output->values + output->row_count * ncols;
+        if (knull) {
+            write_str_sum_null_row(dst, nagg, th, sum_slot, agg_is_sum1,
+                                   val_is_double);
+        } else {
+            const OutStrGroup& g = hgroups[gI];
+            const uint32_t klen = (uint32_t)(g.off_len & 0xFFFFFF);
+            if (output->string_pool_used + klen > output->string_pool_capacity) {
+                set_err(errbuf, errlen, "string pool too small");
+                return YT_ERR_CAPACITY;
+            }
+            char* kdst = output->string_pool + output->string_pool_used;
+            memcpy(kdst, pool.data() + (g.off_len >> 24), klen);
+            write_str_sum_row(dst, nagg, YT_VT_STRING, klen, kdst,
+                              g.cnt_nonnull & 0xFFFFFFFFULL, g.cnt_nonnull >> 32,
+                              g.sum_bits, agg_is_sum1, val_is_double);
+            output->string_pool_used += klen;
+        }
+        output->row_count++;
+    }
+    return YT_OK;
+}
+
 /* string-keyed GROUP BY (config-5 family). Dense per-segment dictionary-id
  * accumulators, then an exact cross-segment merge (hash gate + byte
  * compare), then device-side key materialization into the caller's string
@@ -3467,66 +3794,13 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
                             char* errbuf, size_t errlen,
                             StrPartialOut* po = nullptr)
 {
-    int rc = YT_OK;
-    int sum_slot = -1, sum_col = -1, val_is_double = 0;
-    bool general = plan->filter != nullptr;
-    uint8_t col_types[kMaxCols];
-    memset(col_types, YT_VT_INT64, sizeof(col_types));
-    for (int c = 0; c < chunk->column_count && c < kMaxCols; c++)
-        col_types[c] = (uint8_t)chunk->columns[c].value_type;
-    for (int a = 0; a < plan->agg_count; a++) {
-        int f = plan->aggs[a]->func;
-        if (f == YT_AGG_SUM) {
-            int c;
-            if (sum_slot >= 0) {
-                if (po) {
-                    set_err(errbuf, errlen,
-                            "partial_str: the string state row carries one sum");
-                    return YT_ERR_UNSUPPORTED;
-                }
-                general = true;
-                continue;
-            }
-            sum_slot = a;
-            if (expr_is_col(plan->aggs[a]->arg, &c) && c >= 0 &&
-                c < chunk->column_count && c < kMaxCols) {
-                sum_col = c;
-                val_is_double = col_types[c] == YT_VT_DOUBLE;
-                if (!val_is_double && col_types[c] != YT_VT_INT64) general = true;
-            } else {
-                general = true;     /* sum(<expression>) */
-            }
-        } else if (f != YT_AGG_SUM1) {
-            if (po) {
-                set_err(errbuf, errlen,
-                        "partial_str: min/max/avg/first are not exchanged for "
-                        "string keys (the state row carries sum and sum(1))");
-                return YT_ERR_UNSUPPORTED;
-            }
-            general = true;
-        }
-    }
-    if (plan->project_count) {
-        set_err(errbuf, errlen, "string keys: no post-projection this round");
-        return YT_ERR_UNSUPPORTED;
-    }
-    /* key layout and segmentation decide too (host-visible segment meta) */
-    {
-        const YtColumn& kcol = chunk->columns[key_col];
-        for (int i = 0; i < kcol.segment_count; i++) {
-            if (kcol.segments[i].type == YT_SEG_DIRECT_RLE) general = true;
-            if (i + 1 < kcol.segment_count &&
-                kcol.segments[i].row_count != kcol.segments[0].row_count)
-                general = true;
-        }
-        if (!general && sum_col >= 0) {
-            const YtColumn& vcol = chunk->columns[sum_col];
-            if (vcol.segment_count != kcol.segment_count) general = true;
-            for (int i = 0; !general && i < kcol.segment_count; i++)
-                if (vcol.segments[i].row_count != kcol.segments[i].row_count)
-                    general = true;
-        }
-    }
+    StrGroupShape sh;
+    int rc = classify_string_group(plan, chunk, key_col, po != nullptr, &sh,
+                                   errbuf, errlen);
+    if (rc) return rc;
+    const bool general = sh.general;
+    const int sum_slot = sh.sum_slot, sum_col = sh.sum_col;
+    int val_is_double = sh.val_is_double;
     DevPlan dp;
     StrPreds SP;
     uint8_t sum_type[kMaxAggs];
@@ -3538,7 +3812,7 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
         if (rc) return rc;
         for (int a = 0; a < plan->agg_count; a++) {
             sum_type[a] = (plan->aggs[a]->func != YT_AGG_SUM1)
-                ? expr_static_type(plan->aggs[a]->arg, col_types)
+                ? expr_static_type(plan->aggs[a]->arg, sh.col_types)
                 : (uint8_t)YT_VT_INT64;
             if (sum_type[a] == YT_VT_NULL) sum_type[a] = YT_VT_INT64;
         }
@@ -3555,6 +3829,7 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
     t_last_scan_path = general ? YT_SCAN_PATH_STR_GENERAL : YT_SCAN_PATH_STR_DENSE;
 
     DeviceRun R;
+    PoolScope ps;
     R.stream = (hipStream_t)(uintptr_t)options->stream;
     unsigned mw = 0;
     int in_clamped = 0;
@@ -3584,641 +3859,305 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
     }
 
     /* read back the parsed key-column segments: dictionary sizes + layout */
-    int knseg = R.h_cnt[key_col];
-    int koff = R.h_off[key_col];
+    const int knseg = R.h_cnt[key_col];
+    const int koff = R.h_off[key_col];
     std::vector<SegEx> ksegex(knseg);
     TableHdr th;
     int64_t total_dict = 0;
-    {
-        HIP_CHECK(hipMemcpy(ksegex.data(), R.d_segex + koff,
-                            sizeof(SegEx) * knseg, hipMemcpyDeviceToHost));
-        for (int i = 0; i < knseg; i++) {
-            if (!(ksegex[i].flags & (general ? (8 | 32 | 64) : (8 | 32)))) {
-                set_err(errbuf, errlen, "string keys: unknown key segment layout");
-                return YT_ERR_UNSUPPORTED;
-            }
-        }
-        int32_t rows0 = R.h_segs[koff].row_count;
-        /* accumulator record: {cnt|nonnull<<32, sum} on the specialised
-         * path, {rows, {bits, nonnull} per aggregate} on the general one */
-        const int acc_stride = general ? 1 + 2 * plan->agg_count : 2;
-        /* rows actually scanned (input_row_limit clamps the segment list) */
-        const int64_t scan_rows = R.h_segs[koff + knseg - 1].start_row
-                                + R.h_segs[koff + knseg - 1].row_count;
-        if (general && po && scan_rows >= ((int64_t)1 << 32)) {
-            set_err(errbuf, errlen, "partial_str: chunk too large (2^32 rows)");
+    HIP_CHECK(hipMemcpy(ksegex.data(), R.d_segex + koff,
+                        sizeof(SegEx) * knseg, hipMemcpyDeviceToHost));
+    for (int i = 0; i < knseg; i++) {
+        if (!(ksegex[i].flags & (general ? (8 | 32 | 64) : (8 | 32)))) {
+            set_err(errbuf, errlen, "string keys: unknown key segment layout");
             return YT_ERR_UNSUPPORTED;
         }
+    }
+    const int32_t rows0 = R.h_segs[koff].row_count;
+    /* accumulator record: {cnt|nonnull<<32, sum} on the specialised
+     * path, {rows, {bits, nonnull} per aggregate} on the general one */
+    const int acc_stride = general ? 1 + 2 * plan->agg_count : 2;
+    /* rows actually scanned (input_row_limit clamps the segment list) */
+    const int64_t scan_rows = R.h_segs[koff + knseg - 1].start_row
+                            + R.h_segs[koff + knseg - 1].row_count;
+    if (general && po && scan_rows >= ((int64_t)1 << 32)) {
+        set_err(errbuf, errlen, "partial_str: chunk too large (2^32 rows)");
+        return YT_ERR_UNSUPPORTED;
+    }
 
-        std::vector<int64_t> acc_base(knseg + 1);
-        for (int i = 0; i < knseg; i++) {
-            acc_base[i] = total_dict;
-            total_dict += ksegex[i].dict_size;
+    std::vector<int64_t> acc_base(knseg + 1);
+    for (int i = 0; i < knseg; i++) {
+        acc_base[i] = total_dict;
+        total_dict += ksegex[i].dict_size;
+    }
+    acc_base[knseg] = total_dict;
+
+    StrGroupParams sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.key_seg_off = koff;
+    sp.key_seg_cnt = knseg;
+    sp.val_seg_off = sum_col >= 0 ? R.h_off[sum_col] : -1;
+    sp.val_seg_cnt = sum_col >= 0 ? R.h_cnt[sum_col] : 0;
+    sp.val_is_double = val_is_double;
+    sp.sum_slot = sum_slot;
+    sp.agg_count = plan->agg_count;
+    sp.has_val_nulls = sum_col >= 0 && (R.col_null_flags[sum_col] != 0);
+    sp.tile_rows = 8192;
+    if (sp.tile_rows > rows0) sp.tile_rows = rows0 > 256 ? rows0 : 256;
+    sp.tiles_per_seg = (rows0 + sp.tile_rows - 1) / sp.tile_rows;
+    {
+        const char* sa = getenv("YTQL_STRACCUM");
+        sp.xcd_affine = sa ? atoi(sa) : 1;
+    }
+    const int32_t last_rows = R.h_segs[koff + knseg - 1].row_count;
+    sp.ntiles = (knseg - 1) * sp.tiles_per_seg
+              + (last_rows + sp.tile_rows - 1) / sp.tile_rows;
+    sp.row_count = chunk->row_count;
+
+    int64_t* d_accbase = nullptr;
+    unsigned long long* d_acc = nullptr;
+    uint64_t* d_hashes = nullptr;
+    StrSlot* d_slots = nullptr;
+    HIP_CHECK(ps.dev(&d_accbase, sizeof(int64_t) * (knseg + 1)));
+    HIP_CHECK(hipMemcpyAsync(d_accbase, acc_base.data(),
+                             sizeof(int64_t) * (knseg + 1),
+                             hipMemcpyHostToDevice, R.stream));
+    HIP_CHECK(ps.dev(&d_acc, sizeof(uint64_t) * acc_stride * (total_dict ? total_dict : 1)));
+    HIP_CHECK(hipMemsetAsync(d_acc, 0, sizeof(uint64_t) * acc_stride * (total_dict ? total_dict : 1), R.stream));
+    HIP_CHECK(ps.dev(&d_hashes, sizeof(uint64_t) * (total_dict ? total_dict : 1)));
+    /* per-entry identity + prefix arrays: filled by the hash kernel so
+     * the merge's hot path reads them as a stream (YTQL_STRMERGE=0
+     * falls back to the round-1 dict-read probe for A/B) */
+    uint64_t* d_idents = nullptr;
+    ulonglong2* d_pfxs = nullptr;
+    HIP_CHECK(ps.dev(&d_idents, sizeof(uint64_t) * (total_dict ? total_dict : 1)));
+    HIP_CHECK(ps.dev(&d_pfxs, sizeof(ulonglong2) * (total_dict ? total_dict : 1)));
+    const char* sm_env = getenv("YTQL_STRMERGE");
+    const int merge_fast = sm_env ? atoi(sm_env) : 1;
+    /* Table sized for the worst case (every dict entry distinct).
+     * Measured: an 8×-smaller table holding just the ~6 M live keys is
+     * NOT faster — the merge's scattered atomics then fight over hot
+     * cachelines across XCDs (59 ms vs 47 ms at 86 M entries), while
+     * the oversized cold table costs only compact-scan time, which the
+     * two-pass compact already made cheap. The grow-on-overflow loop
+     * below is kept as a safety net (never triggers at this size). */
+    uint64_t nslots_cap = next_pow2((uint64_t)(total_dict ? total_dict : 1) * 2);
+    if (nslots_cap < 2048) nslots_cap = 2048;
+    /* Start smaller than the every-entry-distinct worst case: the 64 B/slot
+     * table is memset before the merge and scanned by the compact, so an
+     * oversized table costs real milliseconds per step. With a caller
+     * hint, 2x the hint; otherwise half the entry count (cross-segment
+     * duplication >= 2x in any chunk where a GROUP BY is the right
+     * plan). The grow-on-overflow loop below keeps correctness for
+     * adversarial cardinalities (one 4x retry reaches 2x entries). */
+    const char* sx_env = getenv("YTQL_STRSLOTS_X");
+    uint64_t slots_x = sx_env ? (uint64_t)atoll(sx_env) : 4;
+    if (slots_x < 1) slots_x = 1;
+    uint64_t nslots = options->max_groups_hint > 0
+        ? next_pow2((uint64_t)options->max_groups_hint * slots_x)
+        : next_pow2((uint64_t)(total_dict ? total_dict : 1) / 2 + 1);
+    if (nslots < 2048) nslots = 2048;
+    if (nslots > nslots_cap) nslots = nslots_cap;
+    HIP_CHECK(ps.dev(&d_slots, sizeof(StrSlot) * nslots));
+    HIP_CHECK(hipMemsetAsync(d_slots, 0, sizeof(StrSlot) * nslots, R.stream));
+    /* general path: one aggregate record per slot, beside the slot table
+     * (the slot line itself stays 64 B) */
+    unsigned long long* d_slotaggs = nullptr;
+    OutStrAgg* d_oaggs = nullptr;
+    OutStrAgg* haggs = nullptr;
+    StrGenAggs ag;
+    memset(&ag, 0, sizeof(ag));
+    if (general) {
+        ag.count = plan->agg_count;
+        for (int a = 0; a < plan->agg_count; a++) {
+            ag.func[a] = plan->aggs[a]->func;
+            ag.is_double[a] = sum_type[a] == YT_VT_DOUBLE;
         }
-        acc_base[knseg] = total_dict;
+        HIP_CHECK(ps.dev(&d_slotaggs, sizeof(uint64_t) * acc_stride * nslots));
+        HIP_CHECK(hipMemsetAsync(d_slotaggs, 0,
+                                 sizeof(uint64_t) * acc_stride * nslots, R.stream));
+    }
 
-        StrGroupParams sp;
-        memset(&sp, 0, sizeof(sp));
-        sp.key_seg_off = koff;
-        sp.key_seg_cnt = knseg;
-        sp.val_seg_off = sum_col >= 0 ? R.h_off[sum_col] : -1;
-        sp.val_seg_cnt = sum_col >= 0 ? R.h_cnt[sum_col] : 0;
-        sp.val_is_double = val_is_double;
-        sp.sum_slot = sum_slot;
-        sp.agg_count = plan->agg_count;
-        sp.has_val_nulls = sum_col >= 0 && (R.col_null_flags[sum_col] != 0);
-        sp.tile_rows = 8192;
-        if (sp.tile_rows > rows0) sp.tile_rows = rows0 > 256 ? rows0 : 256;
-        sp.tiles_per_seg = (rows0 + sp.tile_rows - 1) / sp.tile_rows;
-        {
-            const char* sa = getenv("YTQL_STRACCUM");
-            sp.xcd_affine = sa ? atoi(sa) : 1;
-        }
-        int32_t last_rows = R.h_segs[koff + knseg - 1].row_count;
-        sp.ntiles = (knseg - 1) * sp.tiles_per_seg
-                  + (last_rows + sp.tile_rows - 1) / sp.tile_rows;
-        sp.row_count = chunk->row_count;
-
-        int64_t* d_accbase = nullptr;
-        unsigned long long* d_acc = nullptr;
-        uint64_t* d_hashes = nullptr;
-        StrSlot* d_slots = nullptr;
-        HIP_CHECK(pool_alloc(&d_accbase, sizeof(int64_t) * (knseg + 1)));
-        HIP_CHECK(hipMemcpyAsync(d_accbase, acc_base.data(),
-                                 sizeof(int64_t) * (knseg + 1),
-                                 hipMemcpyHostToDevice, R.stream));
-        HIP_CHECK(pool_alloc(&d_acc, sizeof(uint64_t) * acc_stride * (total_dict ? total_dict : 1)));
-        HIP_CHECK(hipMemsetAsync(d_acc, 0, sizeof(uint64_t) * acc_stride * (total_dict ? total_dict : 1), R.stream));
-        HIP_CHECK(pool_alloc(&d_hashes, sizeof(uint64_t) * (total_dict ? total_dict : 1)));
-        /* per-entry identity + prefix arrays: filled by the hash kernel so
-         * the merge's hot path reads them as a stream (YTQL_STRMERGE=0
-         * falls back to the round-1 dict-read probe for A/B) */
-        uint64_t* d_idents = nullptr;
-        ulonglong2* d_pfxs = nullptr;
-        HIP_CHECK(pool_alloc(&d_idents, sizeof(uint64_t) * (total_dict ? total_dict : 1)));
-        HIP_CHECK(pool_alloc(&d_pfxs, sizeof(ulonglong2) * (total_dict ? total_dict : 1)));
-        const char* sm_env = getenv("YTQL_STRMERGE");
-        int merge_fast = sm_env ? atoi(sm_env) : 1;
-        /* Table sized for the worst case (every dict entry distinct).
-         * Measured: an 8×-smaller table holding just the ~6 M live keys is
-         * NOT faster — the merge's scattered atomics then fight over hot
-         * cachelines across XCDs (59 ms vs 47 ms at 86 M entries), while
-         * the oversized cold table costs only compact-scan time, which the
-         * two-pass compact already made cheap. The grow-on-overflow loop
-         * below is kept as a safety net (never triggers at this size). */
-        uint64_t nslots_cap = next_pow2((uint64_t)(total_dict ? total_dict : 1) * 2);
-        if (nslots_cap < 2048) nslots_cap = 2048;
-        /* Start smaller than the every-entry-distinct worst case: the 64 B/slot
-         * table is memset before the merge and scanned by the compact, so an
-         * oversized table costs real milliseconds per step. With a caller
-         * hint, 2x the hint; otherwise half the entry count (cross-segment
-         * duplication >= 2x in any chunk where a GROUP BY is the right
-         * plan). The grow-on-overflow loop below keeps correctness for
-         * adversarial cardinalities (one 4x retry reaches 2x entries). */
-        const char* sx_env = getenv("YTQL_STRSLOTS_X");
-        uint64_t slots_x = sx_env ? (uint64_t)atoll(sx_env) : 4;
-        if (slots_x < 1) slots_x = 1;
-        uint64_t nslots = options->max_groups_hint > 0
-            ? next_pow2((uint64_t)options->max_groups_hint * slots_x)
-            : next_pow2((uint64_t)(total_dict ? total_dict : 1) / 2 + 1);
-        if (nslots < 2048) nslots = 2048;
-        if (nslots > nslots_cap) nslots = nslots_cap;
-        HIP_CHECK(pool_alloc(&d_slots, sizeof(StrSlot) * nslots));
-        HIP_CHECK(hipMemsetAsync(d_slots, 0, sizeof(StrSlot) * nslots, R.stream));
-        /* general path: one aggregate record per slot, beside the slot table
-         * (the slot line itself stays 64 B) */
-        unsigned long long* d_slotaggs = nullptr;
-        OutStrAgg* d_oaggs = nullptr;
-        OutStrAgg* haggs = nullptr;
-        StrGenAggs ag;
-        memset(&ag, 0, sizeof(ag));
+    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, ea = nullptr, eh = nullptr;
+    HIP_CHECK(ps.event(&e0));
+    HIP_CHECK(ps.event(&e1));
+    HIP_CHECK(ps.event(&e2));
+    HIP_CHECK(ps.event(&ea));
+    HIP_CHECK(ps.event(&eh));
+    HIP_CHECK(hipEventRecord(e0, R.stream));
+    if (general) {
+        HIP_CHECK(ytql_launch_strgen_accum(&dp, R.d_segs, R.d_segex, R.d_off,
+                                           R.d_cnt, key_col, scan_rows,
+                                           d_accbase, d_acc, R.d_th, R.d_err,
+                                           R.stream));
+    } else {
+        HIP_CHECK(ytql_launch_strgrp_accum(&sp, R.d_segs, R.d_segex, d_accbase,
+                                           d_acc, R.d_th, R.stream));
+    }
+    HIP_CHECK(hipEventRecord(ea, R.stream));
+    HIP_CHECK(ytql_launch_strgrp_hash(R.d_segs, R.d_segex, koff, knseg,
+                                      d_accbase, d_hashes, d_idents, d_pfxs,
+                                      total_dict, R.stream));
+    HIP_CHECK(hipEventRecord(eh, R.stream));
+    for (;;) {
         if (general) {
-            ag.count = plan->agg_count;
-            for (int a = 0; a < plan->agg_count; a++) {
-                ag.func[a] = plan->aggs[a]->func;
-                ag.is_double[a] = sum_type[a] == YT_VT_DOUBLE;
-            }
-            HIP_CHECK(pool_alloc(&d_slotaggs, sizeof(uint64_t) * acc_stride * nslots));
-            HIP_CHECK(hipMemsetAsync(d_slotaggs, 0,
-                                     sizeof(uint64_t) * acc_stride * nslots, R.stream));
-        }
-
-        hipEvent_t e0, e1, e2, ea, eh;
-        HIP_CHECK(hipEventCreate(&e0));
-        HIP_CHECK(hipEventCreate(&e1));
-        HIP_CHECK(hipEventCreate(&e2));
-        HIP_CHECK(hipEventCreate(&ea));
-        HIP_CHECK(hipEventCreate(&eh));
-        HIP_CHECK(hipEventRecord(e0, R.stream));
-        if (general) {
-            HIP_CHECK(ytql_launch_strgen_accum(&dp, R.d_segs, R.d_segex, R.d_off,
-                                               R.d_cnt, key_col, scan_rows,
-                                               d_accbase, d_acc, R.d_th, R.d_err,
+            HIP_CHECK(ytql_launch_strgen_merge(R.d_segs, R.d_segex, koff, knseg,
+                                               d_accbase, d_acc, &ag, d_hashes,
+                                               d_idents, d_pfxs, d_slots, nslots,
+                                               d_slotaggs, R.d_th, total_dict,
                                                R.stream));
         } else {
-            HIP_CHECK(ytql_launch_strgrp_accum(&sp, R.d_segs, R.d_segex, d_accbase,
-                                               d_acc, R.d_th, R.stream));
+            HIP_CHECK(ytql_launch_strgrp_merge(R.d_segs, R.d_segex, koff, knseg,
+                                               d_accbase, d_acc, d_hashes,
+                                               d_idents, d_pfxs,
+                                               d_slots, nslots, val_is_double,
+                                               merge_fast, R.d_th, total_dict,
+                                               R.stream));
         }
-        HIP_CHECK(hipEventRecord(ea, R.stream));
-        HIP_CHECK(ytql_launch_strgrp_hash(R.d_segs, R.d_segex, koff, knseg,
-                                          d_accbase, d_hashes, d_idents, d_pfxs,
-                                          total_dict, R.stream));
-        HIP_CHECK(hipEventRecord(eh, R.stream));
-        for (;;) {
-            if (general) {
-                HIP_CHECK(ytql_launch_strgen_merge(R.d_segs, R.d_segex, koff, knseg,
-                                                   d_accbase, d_acc, &ag, d_hashes,
-                                                   d_idents, d_pfxs, d_slots, nslots,
-                                                   d_slotaggs, R.d_th, total_dict,
-                                                   R.stream));
-            } else {
-                HIP_CHECK(ytql_launch_strgrp_merge(R.d_segs, R.d_segex, koff, knseg,
-                                                   d_accbase, d_acc, d_hashes,
-                                                   d_idents, d_pfxs,
-                                                   d_slots, nslots, val_is_double,
-                                                   merge_fast, R.d_th, total_dict,
-                                                   R.stream));
-            }
-            HIP_CHECK(hipMemcpy(&th, R.d_th, sizeof(th), hipMemcpyDeviceToHost));
-            if (th.overflow != 1 || nslots >= nslots_cap) break;
-            g_pool.put(d_slots);
-            nslots *= 4;
-            if (nslots > nslots_cap) nslots = nslots_cap;
-            HIP_CHECK(pool_alloc(&d_slots, sizeof(StrSlot) * nslots));
-            HIP_CHECK(hipMemsetAsync(d_slots, 0, sizeof(StrSlot) * nslots, R.stream));
-            if (general) {
-                g_pool.put(d_slotaggs);
-                d_slotaggs = nullptr;
-                HIP_CHECK(pool_alloc(&d_slotaggs, sizeof(uint64_t) * acc_stride * nslots));
-                HIP_CHECK(hipMemsetAsync(d_slotaggs, 0,
-                                         sizeof(uint64_t) * acc_stride * nslots,
-                                         R.stream));
-            }
-            th.ngroups = 0;
-            th.overflow = 0;
-            HIP_CHECK(hipMemcpy(R.d_th, &th, sizeof(th), hipMemcpyHostToDevice));
-        }
-        HIP_CHECK(hipEventRecord(e1, R.stream));
-        if (general) {
-            /* expression errors raised by the accumulate kernel */
-            unsigned kerr = 0;
-            HIP_CHECK(hipMemcpy(&kerr, R.d_err, sizeof(unsigned), hipMemcpyDeviceToHost));
-            if (kerr) {
-                g_pool.put(d_accbase); g_pool.put(d_acc); g_pool.put(d_hashes);
-                g_pool.put(d_idents); g_pool.put(d_pfxs); g_pool.put(d_slots);
-                g_pool.put(d_slotaggs);
-                (void)hipEventDestroy(ea); (void)hipEventDestroy(eh);
-                (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-                (void)hipEventDestroy(e2);
-                set_err(errbuf, errlen, kerr == YT_ERR_DIV_ZERO
-                        ? "Division by zero" : "expression error");
-                return (int)kerr;
-            }
-        }
-
-        /* compact + materialize keys into a device pool */
-        int64_t ngroups = (int64_t)th.ngroups;
-        uint64_t pool_cap = 0;
-        for (int i = 0; i < knseg; i++) {
-            /* dictionary blob bytes upper-bound the key bytes */
-            pool_cap += (uint64_t)R.h_segs[koff + i].blob_bytes;
-        }
-        if (pool_cap < 1024) pool_cap = 1024;
-        OutStrGroup* d_out = nullptr;
-        char* d_pool = nullptr;
-        unsigned long long* d_ctr = nullptr;
-        HIP_CHECK(pool_alloc(&d_out, sizeof(OutStrGroup) * (ngroups ? ngroups : 1)));
-        HIP_CHECK(pool_alloc(&d_pool, pool_cap));
-        HIP_CHECK(pool_alloc(&d_ctr, 2 * sizeof(unsigned long long)));
-        HIP_CHECK(hipMemsetAsync(d_ctr, 0, 2 * sizeof(unsigned long long), R.stream));
-        if (ngroups > 0) {
-            HIP_CHECK(ytql_launch_strgrp_compact(R.d_segs, R.d_segex, koff,
-                                                 d_slots, nslots, d_out, d_ctr,
-                                                 d_pool, d_ctr + 1, pool_cap,
-                                                 R.d_th, R.stream));
-        }
-        if (general) {
-            /* compact copied each slot's index (left in StrSlot.sum_bits by
-             * the merge) into OutStrGroup.sum_bits: gather the aggregate
-             * records in group order. The bottom query also packs them back
-             * into the {sum, cnt|nonnull} form the partition kernels read —
-             * 32-bit halves, so it needs the chunk below 2^32 rows. */
-            HIP_CHECK(pool_alloc(&d_oaggs, sizeof(OutStrAgg) * (ngroups ? ngroups : 1)));
-            HIP_CHECK(pool_alloc_host(&haggs, sizeof(OutStrAgg) * (ngroups ? ngroups : 1)));
-            if (ngroups > 0) {
-                HIP_CHECK(ytql_launch_strgen_gather(d_out, ngroups, d_slotaggs,
-                                                    nslots, plan->agg_count,
-                                                    d_oaggs, po ? 1 : 0, sum_slot,
-                                                    R.stream));
-                HIP_CHECK(hipMemcpyAsync(haggs, d_oaggs, sizeof(OutStrAgg) * ngroups,
-                                         hipMemcpyDeviceToHost, R.stream));
-            }
-        }
-        OutStrGroup* hgroups = nullptr;
-        HIP_CHECK(pool_alloc_host(&hgroups,
-                                  sizeof(OutStrGroup) * (ngroups ? ngroups : 1)));
-        unsigned long long hctr[2] = {0, 0};
-        /* the fast emit path below streams hgroups in SLICES so the host
-         * emit overlaps the remaining D2H; the limited path copies here */
-        HIP_CHECK(hipMemcpyAsync(hctr, d_ctr, 2 * sizeof(unsigned long long),
-                                 hipMemcpyDeviceToHost, R.stream));
-        HIP_CHECK(hipEventRecord(e2, R.stream));
-        HIP_CHECK(hipStreamSynchronize(R.stream));
-        float ms = 0, ms_other = 0;
-        HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        HIP_CHECK(hipEventElapsedTime(&ms_other, e1, e2));
-        if (getenv("YTQL_TIMING")) {
-            float ms_acc = 0, ms_hash = 0;
-            HIP_CHECK(hipEventElapsedTime(&ms_acc, e0, ea));
-            HIP_CHECK(hipEventElapsedTime(&ms_hash, ea, eh));
-            fprintf(stderr, "[ytql timing] strgrp%s: accum %.2fms hash %.2fms "
-                    "merge %.2fms compact+D2H %.2fms\n",
-                    general ? " (general)" : "",
-                    ms_acc, ms_hash, ms - ms_acc - ms_hash, ms_other);
-        }
-        (void)hipEventDestroy(ea);
-        (void)hipEventDestroy(eh);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        (void)hipEventDestroy(e2);
         HIP_CHECK(hipMemcpy(&th, R.d_th, sizeof(th), hipMemcpyDeviceToHost));
-        if (th.overflow == 1) {
-            g_pool.put(d_accbase); g_pool.put(d_acc); g_pool.put(d_hashes);
-            g_pool.put(d_idents); g_pool.put(d_pfxs);
-            g_pool.put(d_slots); g_pool.put(d_out); g_pool.put(d_pool);
-            g_pool.put(d_ctr); g_pool.put(hgroups);
-            g_pool.put(d_slotaggs); g_pool.put(d_oaggs); g_pool.put(haggs);
-            set_err(errbuf, errlen, "string merge table/pool overflow");
-            return YT_ERR_CAPACITY;
-        }
-
-        if (po) {
-            /* bottom query: hash-partition the compacted groups + the null
-             * side group into state rows and per-partition pool slices
-             * (key_bits = slice-local offset<<24 | len) */
-            auto putall = [&]() {
-                g_pool.put(d_accbase); g_pool.put(d_acc); g_pool.put(d_hashes);
-                g_pool.put(d_idents); g_pool.put(d_pfxs);
-                g_pool.put(d_slots); g_pool.put(d_out); g_pool.put(d_pool);
-                g_pool.put(d_ctr); g_pool.put(hgroups);
-                g_pool.put(d_slotaggs); g_pool.put(d_oaggs); g_pool.put(haggs);
-            };
-            const int np = po->partition_count;
-            const int p_null = (int)(splitmix64_host(
-                0xCBF29CE484222325ULL ^ 0xDEADBEEF12345678ULL) % (uint64_t)np);
-            unsigned long long* d_pc = nullptr;   /* [np] counts, [np] bytes,
-                                                     [np] cursors, [np] bcursors,
-                                                     [np] pool_base */
-            HIP_CHECK(pool_alloc(&d_pc, sizeof(unsigned long long) * np * 5));
-            HIP_CHECK(hipMemsetAsync(d_pc, 0,
-                                     sizeof(unsigned long long) * np * 5,
-                                     R.stream));
-            if (ngroups > 0) {
-                HIP_CHECK(ytql_launch_strst_count(d_out, ngroups, d_pool, np,
-                                                  d_pc, d_pc + np, R.stream));
-            }
-            std::vector<unsigned long long> pc(2 * np);
-            HIP_CHECK(hipMemcpyAsync(pc.data(), d_pc,
-                                     sizeof(unsigned long long) * 2 * np,
-                                     hipMemcpyDeviceToHost, R.stream));
-            HIP_CHECK(hipStreamSynchronize(R.stream));
-            if (th.side_used[1]) pc[p_null] += 1;
-            unsigned long long rrun = 0, brun = 0;
-            std::vector<unsigned long long> rcur(np), pbase(np);
-            for (int p = 0; p < np; p++) {
-                rcur[p] = rrun;
-                pbase[p] = brun;
-                rrun += pc[p];
-                brun += pc[np + p];
-            }
-            if ((int64_t)rrun > po->capacity_rows
-                || (int64_t)brun > po->pool_capacity) {
-                putall();
-                g_pool.put(d_pc);
-                set_err(errbuf, errlen, "partial_str: state/pool buffer too small");
-                return YT_ERR_CAPACITY;
-            }
-            HIP_CHECK(hipMemcpyAsync(d_pc + 2 * np, rcur.data(),
-                                     sizeof(unsigned long long) * np,
-                                     hipMemcpyHostToDevice, R.stream));
-            HIP_CHECK(hipMemsetAsync(d_pc + 3 * np, 0,
-                                     sizeof(unsigned long long) * np, R.stream));
-            HIP_CHECK(hipMemcpyAsync(d_pc + 4 * np, pbase.data(),
-                                     sizeof(unsigned long long) * np,
-                                     hipMemcpyHostToDevice, R.stream));
-            if (ngroups > 0) {
-                HIP_CHECK(ytql_launch_strst_scatter(d_out, ngroups, d_pool, np,
-                                                    val_is_double,
-                                                    d_pc + 2 * np, d_pc + 3 * np,
-                                                    po->states_device,
-                                                    po->pool_device,
-                                                    d_pc + 4 * np, R.stream));
-            }
-            HIP_CHECK(hipStreamSynchronize(R.stream));
-            if (th.side_used[1]) {
-                unsigned long long pos = 0;
-                HIP_CHECK(hipMemcpy(&pos, d_pc + 2 * np + p_null,
-                                    sizeof(pos), hipMemcpyDeviceToHost));
-                YtStateRow sr;
-                memset(&sr, 0, sizeof(sr));
-                sr.key_bits = 0;
-                uint64_t nn = sum_slot >= 0 ? th.side_agg[1][2 * sum_slot + 1] : 0;
-                sr.meta = 1ULL | (val_is_double ? 2ULL : 0ULL) | (nn << 8);
-                sr.sum_bits = sum_slot >= 0 ? th.side_agg[1][2 * sum_slot] : 0;
-                sr.row_count = th.side_cnt[1];
-                HIP_CHECK(hipMemcpy(po->states_device + pos, &sr, sizeof(sr),
-                                    hipMemcpyHostToDevice));
-            }
-            for (int p = 0; p < np; p++) {
-                po->part_counts[p] = (int64_t)pc[p];
-                po->part_pool_bytes[p] = (int64_t)pc[np + p];
-            }
-            if (stats) {
-                stats->rows_read = chunk->row_count;
-                stats->grouped_row_count = (int64_t)rrun;
-                stats->incomplete_input = in_clamped;
-                stats->incomplete_output = (th.overflow == 2);
-                stats->kernel_scan_ms += ms;
-                stats->kernel_scan_launches += 1;
-                stats->kernel_other_ms += ms_other;
-                stats->execute_time_ms = now_ms() - tw0;
-            }
-            putall();
-            g_pool.put(d_pc);
-            return YT_OK;
-        }
-
-        /* emit [key(string), aggs...] rows. Fast path (no output limit,
-         * everything fits): copy the device key pool wholesale — compact's
-         * pool_off values are global offsets into it — and fill the YtValue
-         * rows with host threads. */
-        int ncols = 1 + plan->agg_count;
-        int out_limited = 0;
-        int64_t ng = ngroups;
-        int has_null_row = th.side_used[1] ? 1 : 0;
+        if (th.overflow != 1 || nslots >= nslots_cap) break;
+        ps.release(d_slots);
+        d_slots = nullptr;
+        nslots *= 4;
+        if (nslots > nslots_cap) nslots = nslots_cap;
+        HIP_CHECK(ps.dev(&d_slots, sizeof(StrSlot) * nslots));
+        HIP_CHECK(hipMemsetAsync(d_slots, 0, sizeof(StrSlot) * nslots, R.stream));
         if (general) {
-            std::vector<char> pool(hctr[1] ? hctr[1] : 1);
-            if (hctr[1]) {
-                HIP_CHECK(hipMemcpy(pool.data(), d_pool, hctr[1], hipMemcpyDeviceToHost));
-            }
-            if (ngroups > 0) {
-                HIP_CHECK(hipMemcpy(hgroups, d_out, sizeof(OutStrGroup) * ngroups,
-                                    hipMemcpyDeviceToHost));
-            }
-            rc = emit_string_general(plan, sum_type, hgroups, haggs, ngroups,
-                                     pool.data(), th, options->output_row_limit,
-                                     &out_limited, output, errbuf, errlen);
-            goto emitted;
+            ps.release(d_slotaggs);
+            d_slotaggs = nullptr;
+            HIP_CHECK(ps.dev(&d_slotaggs, sizeof(uint64_t) * acc_stride * nslots));
+            HIP_CHECK(hipMemsetAsync(d_slotaggs, 0,
+                                     sizeof(uint64_t) * acc_stride * nslots,
+                                     R.stream));
         }
-        if (options->output_row_limit == 0 &&
-            ng + has_null_row <= output->capacity_rows &&
-            (unsigned long long)hctr[1] <= (unsigned long long)output->string_pool_capacity &&
-            (output->string_pool != nullptr || hctr[1] == 0)) {
-            /* pipeline: pool D2H first, then hgroups in slices — the
-             * parallel host copies/emits of slice s overlap slice s+1's
-             * D2H (the serial tail was D2H then copy then emit) */
-            char* stage = nullptr;
-            if (hctr[1]) {
-                HIP_CHECK(pool_alloc_host(&stage, hctr[1]));
-                HIP_CHECK(hipMemcpyAsync(stage, d_pool, hctr[1],
-                                         hipMemcpyDeviceToHost, R.stream));
-            }
-            const int kSlices = (ng >= (1 << 21)) ? 8 : 1;
-            std::vector<hipEvent_t> sl_ev(kSlices, nullptr);
-            int64_t per_sl = (ng + kSlices - 1) / kSlices;
-            for (int s2 = 0; s2 < kSlices; s2++) {
-                int64_t b = (int64_t)s2 * per_sl;
-                int64_t e = std::min<int64_t>(ng, b + per_sl);
-                if (b >= e) break;
-                HIP_CHECK(hipMemcpyAsync(hgroups + b, d_out + b,
-                                         sizeof(OutStrGroup) * (e - b),
-                                         hipMemcpyDeviceToHost, R.stream));
-                HIP_CHECK(hipEventCreate(&sl_ev[s2]));
-                HIP_CHECK(hipEventRecord(sl_ev[s2], R.stream));
-            }
-            std::thread pool_thr;
-            if (hctr[1]) {
-                /* pool D2H was queued first — wait for the FIRST slice event
-                 * (>= pool completion), then copy to the caller's pool off
-                 * the critical path */
-                hipEvent_t after_pool = sl_ev[0];
-                if (!after_pool) {
-                    HIP_CHECK(hipStreamSynchronize(R.stream));
-                }
-                size_t total_b = (size_t)hctr[1];
-                char* dst_pool = output->string_pool;
-                pool_thr = std::thread([stage, dst_pool, total_b, after_pool] {
-                    if (after_pool) (void)hipEventSynchronize(after_pool);
-                    int ct = (int)std::min<size_t>(
-                        std::thread::hardware_concurrency(),
-                        (total_b + (64 << 20) - 1) / (64 << 20));
-                    if (ct > 1) {
-                        std::vector<std::thread> cth;
-                        size_t per = (total_b + ct - 1) / ct;
-                        for (int t = 0; t < ct; t++) {
-                            size_t b = (size_t)t * per;
-                            size_t e = std::min(total_b, b + per);
-                            if (b >= e) break;
-                            cth.emplace_back([=] {
-                                memcpy(dst_pool + b, stage + b, e - b);
-                            });
-                        }
-                        for (auto& th2 : cth) th2.join();
-                    } else if (total_b) {
-                        memcpy(dst_pool, stage, total_b);
-                    }
-                });
-            }
-            output->string_pool_used = hctr[1];
-            int agg_is_sum1[kMaxAggs];
-            for (int a = 0; a < plan->agg_count; a++)
-                agg_is_sum1[a] = plan->aggs[a]->func == YT_AGG_SUM1;
-            auto emit_range = [&](int64_t b, int64_t e) {
-                for (int64_t gI = b; gI < e; gI++) {
-                    const OutStrGroup& g = hgroups[gI];
-                    YtValue* dst = output->values + gI * ncols;
-                    dst[0].id = 0;
-                    dst[0].flags = 0;
-                    dst[0].type = YT_VT_STRING;
-                    dst[0].length = (uint32_t)(g.off_len & 0xFFFFFF);
-                    dst[0].data.str = output->string_pool + (g.off_len >> 24);
-                    for (int a = 0; a < plan->agg_count; a++) {
-                        YtValue& v = dst[1 + a];
-                        v.id = (uint16_t)(1 + a);
-                        v.flags = 0;
-                        v.length = 0;
-                        if (agg_is_sum1[a]) {
-                            v.type = YT_VT_INT64;
-                            v.data.bits = g.cnt_nonnull & 0xFFFFFFFFULL;
-                        } else if ((g.cnt_nonnull >> 32) == 0) {
-                            v.type = YT_VT_NULL;
-                            v.data.bits = 0;
-                        } else {
-                            v.type = val_is_double ? YT_VT_DOUBLE : YT_VT_INT64;
-                            v.data.bits = g.sum_bits;
-                        }
-                    }
-                }
-            };
-            {
-                int nt = (int)std::thread::hardware_concurrency();
-                if (nt < 1) nt = 1;
-                if (nt > 64) nt = 64;
-                if (ng < (1 << 16)) nt = 1;
-                std::vector<std::thread> ths;
-                for (int s2 = 0; s2 < kSlices; s2++) {
-                    int64_t sb = (int64_t)s2 * per_sl;
-                    int64_t se = std::min<int64_t>(ng, sb + per_sl);
-                    if (sb >= se) break;
-                    if (sl_ev[s2]) HIP_CHECK(hipEventSynchronize(sl_ev[s2]));
-                    if (nt == 1) {
-                        emit_range(sb, se);
-                        continue;
-                    }
-                    int kt = nt / kSlices > 0 ? nt / kSlices : 1;
-                    int64_t per = (se - sb + kt - 1) / kt;
-                    for (int t = 0; t < kt; t++) {
-                        int64_t b = sb + (int64_t)t * per, e = b + per;
-                        if (b >= se) break;
-                        if (e > se) e = se;
-                        ths.emplace_back(emit_range, b, e);
-                    }
-                }
-                for (auto& t : ths) t.join();
-                if (pool_thr.joinable()) pool_thr.join();
-                for (auto& ev : sl_ev) if (ev) (void)hipEventDestroy(ev);
-                g_pool.put(stage);
-            }
-            output->row_count = ng;
-            if (has_null_row) {
-                YtValue* dst = output->values + output->row_count * ncols;
-                dst[0].id = 0;
-                dst[0].flags = 0;
-                dst[0].type = YT_VT_NULL;
-                dst[0].length = 0;
-                dst[0].data.bits = 0;
-                uint64_t cnt = th.side_cnt[1];
-                uint64_t sum_bits = sum_slot >= 0 ? th.side_agg[1][2 * sum_slot] : 0;
-                uint64_t nonnull = sum_slot >= 0 ? th.side_agg[1][2 * sum_slot + 1] : 0;
-                for (int a = 0; a < plan->agg_count; a++) {
-                    YtValue& v = dst[1 + a];
-                    v.id = (uint16_t)(1 + a);
-                    v.flags = 0;
-                    v.length = 0;
-                    if (plan->aggs[a]->func == YT_AGG_SUM1) {
-                        v.type = YT_VT_INT64;
-                        v.data.bits = cnt;
-                    } else if (nonnull == 0) {
-                        v.type = YT_VT_NULL;
-                        v.data.bits = 0;
-                    } else {
-                        v.type = val_is_double ? YT_VT_DOUBLE : YT_VT_INT64;
-                        v.data.bits = sum_bits;
-                    }
-                }
-                output->row_count++;
-            }
-            goto emitted;
+        th.ngroups = 0;
+        th.overflow = 0;
+        HIP_CHECK(hipMemcpy(R.d_th, &th, sizeof(th), hipMemcpyHostToDevice));
+    }
+    HIP_CHECK(hipEventRecord(e1, R.stream));
+    if (general) {
+        /* expression errors raised by the accumulate kernel */
+        unsigned kerr = 0;
+        HIP_CHECK(hipMemcpy(&kerr, R.d_err, sizeof(unsigned), hipMemcpyDeviceToHost));
+        if (kerr) {
+            set_err(errbuf, errlen, kerr == YT_ERR_DIV_ZERO
+                    ? "Division by zero" : "expression error");
+            return (int)kerr;
         }
-        {
+    }
+
+    /* compact + materialize keys into a device pool */
+    const int64_t ngroups = (int64_t)th.ngroups;
+    uint64_t pool_cap = 0;
+    for (int i = 0; i < knseg; i++) {
+        /* dictionary blob bytes upper-bound the key bytes */
+        pool_cap += (uint64_t)R.h_segs[koff + i].blob_bytes;
+    }
+    if (pool_cap < 1024) pool_cap = 1024;
+    OutStrGroup* d_out = nullptr;
+    char* d_pool = nullptr;
+    unsigned long long* d_ctr = nullptr;
+    HIP_CHECK(ps.dev(&d_out, sizeof(OutStrGroup) * (ngroups ? ngroups : 1)));
+    HIP_CHECK(ps.dev(&d_pool, pool_cap));
+    HIP_CHECK(ps.dev(&d_ctr, 2 * sizeof(unsigned long long)));
+    HIP_CHECK(hipMemsetAsync(d_ctr, 0, 2 * sizeof(unsigned long long), R.stream));
+    if (ngroups > 0) {
+        HIP_CHECK(ytql_launch_strgrp_compact(R.d_segs, R.d_segex, koff,
+                                             d_slots, nslots, d_out, d_ctr,
+                                             d_pool, d_ctr + 1, pool_cap,
+                                             R.d_th, R.stream));
+    }
+    if (general) {
+        /* compact copied each slot's index (left in StrSlot.sum_bits by
+         * the merge) into OutStrGroup.sum_bits: gather the aggregate
+         * records in group order. The bottom query also packs them back
+         * into the {sum, cnt|nonnull} form the partition kernels read —
+         * 32-bit halves, so it needs the chunk below 2^32 rows. */
+        HIP_CHECK(ps.dev(&d_oaggs, sizeof(OutStrAgg) * (ngroups ? ngroups : 1)));
+        HIP_CHECK(ps.host(&haggs, sizeof(OutStrAgg) * (ngroups ? ngroups : 1)));
+        if (ngroups > 0) {
+            HIP_CHECK(ytql_launch_strgen_gather(d_out, ngroups, d_slotaggs,
+                                                nslots, plan->agg_count,
+                                                d_oaggs, po ? 1 : 0, sum_slot,
+                                                R.stream));
+            HIP_CHECK(hipMemcpyAsync(haggs, d_oaggs, sizeof(OutStrAgg) * ngroups,
+                                     hipMemcpyDeviceToHost, R.stream));
+        }
+    }
+    OutStrGroup* hgroups = nullptr;
+    HIP_CHECK(ps.host(&hgroups, sizeof(OutStrGroup) * (ngroups ? ngroups : 1)));
+    unsigned long long hctr[2] = {0, 0};
+    /* the fast emit path streams hgroups in SLICES so the host emit
+     * overlaps the remaining D2H; the limited path copies in one go */
+    HIP_CHECK(hipMemcpyAsync(hctr, d_ctr, 2 * sizeof(unsigned long long),
+                             hipMemcpyDeviceToHost, R.stream));
+    HIP_CHECK(hipEventRecord(e2, R.stream));
+    HIP_CHECK(hipStreamSynchronize(R.stream));
+    float ms = 0, ms_other = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    HIP_CHECK(hipEventElapsedTime(&ms_other, e1, e2));
+    if (getenv("YTQL_TIMING")) {
+        float ms_acc = 0, ms_hash = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms_acc, e0, ea));
+        HIP_CHECK(hipEventElapsedTime(&ms_hash, ea, eh));
+        fprintf(stderr, "[ytql timing] strgrp%s: accum %.2fms hash %.2fms "
+                "merge %.2fms compact+D2H %.2fms\n",
+                general ? " (general)" : "",
+                ms_acc, ms_hash, ms - ms_acc - ms_hash, ms_other);
+    }
+    HIP_CHECK(hipMemcpy(&th, R.d_th, sizeof(th), hipMemcpyDeviceToHost));
+    if (th.overflow == 1) {
+        set_err(errbuf, errlen, "string merge table/pool overflow");
+        return YT_ERR_CAPACITY;
+    }
+
+    if (po) {
+        int64_t state_rows = 0;
+        rc = partition_string_groups(ps, po, R.stream, d_out, ngroups, d_pool,
+                                     th, sum_slot, val_is_double, &state_rows,
+                                     errbuf, errlen);
+        if (rc) return rc;
+        if (stats) {
+            stats->rows_read = chunk->row_count;
+            stats->grouped_row_count = state_rows;
+            stats->incomplete_input = in_clamped;
+            stats->incomplete_output = (th.overflow == 2);
+            stats->kernel_scan_ms += ms;
+            stats->kernel_scan_launches += 1;
+            stats->kernel_other_ms += ms_other;
+            stats->execute_time_ms = now_ms() - tw0;
+        }
+        return YT_OK;
+    }
+
+    int out_limited = 0;
+    if (general) {
         std::vector<char> pool(hctr[1] ? hctr[1] : 1);
         if (hctr[1]) {
             HIP_CHECK(hipMemcpy(pool.data(), d_pool, hctr[1], hipMemcpyDeviceToHost));
         }
         if (ngroups > 0) {
-            /* the fast path streams hgroups in slices; this limited path
-             * copies them in one go */
             HIP_CHECK(hipMemcpy(hgroups, d_out, sizeof(OutStrGroup) * ngroups,
                                 hipMemcpyDeviceToHost));
         }
-        for (int64_t gI = 0; gI < ngroups + 2; gI++) {
-            const char* kstr = nullptr;
-            uint32_t klen = 0;
-            int knull = 0;
-            uint64_t cnt, sum_bits, nonnull;
-            if (gI < ngroups) {
-                const OutStrGroup& g = hgroups[gI];
-                kstr = pool.data() + (g.off_len >> 24);
-                klen = (uint32_t)(g.off_len & 0xFFFFFF);
-                cnt = g.cnt_nonnull & 0xFFFFFFFFULL;
-                sum_bits = g.sum_bits;
-                nonnull = g.cnt_nonnull >> 32;
-            } else {
-                int side = (int)(gI - ngroups);
-                if (side == 0) continue;                /* no sentinel for strings */
-                if (!th.side_used[1]) continue;
-                knull = 1;
-                cnt = th.side_cnt[1];
-                sum_bits = sum_slot >= 0 ? th.side_agg[1][2 * sum_slot] : 0;
-                nonnull = sum_slot >= 0 ? th.side_agg[1][2 * sum_slot + 1] : 0;
-            }
-            if (options->output_row_limit > 0 &&
-                output->row_count >= options->output_row_limit) {
-                out_limited = 1;
-                break;
-            }
-            if (output->row_count >= output->capacity_rows) {
-                rc = YT_ERR_CAPACITY;
-                break;
-            }
-            YtValue* dst = output->values + output->row_count * ncols;
-            if (knull) {
-                dst[0].type = YT_VT_NULL;
-                dst[0].length = 0;
-                dst[0].data.bits = 0;
-            } else {
-                if (output->string_pool_used + klen > output->string_pool_capacity) {
-                    rc = YT_ERR_CAPACITY;
-                    set_err(errbuf, errlen, "string pool too small");
-                    break;
-                }
-                memcpy(output->string_pool + output->string_pool_used, kstr, klen);
-                dst[0].type = YT_VT_STRING;
-                dst[0].length = klen;
-                dst[0].data.str = output->string_pool + output->string_pool_used;
-                output->string_pool_used += klen;
-            }
-            dst[0].id = 0;
-            dst[0].flags = 0;
-            for (int a = 0; a < plan->agg_count; a++) {
-                YtValue& v = dst[1 + a];
-                v.id = (uint16_t)(1 + a);
-                v.flags = 0;
-                v.length = 0;
-                if (plan->aggs[a]->func == YT_AGG_SUM1) {
-                    v.type = YT_VT_INT64;
-                    v.data.bits = cnt;
-                } else if (nonnull == 0) {
-                    v.type = YT_VT_NULL;
-                    v.data.bits = 0;
-                } else {
-                    v.type = val_is_double ? YT_VT_DOUBLE : YT_VT_INT64;
-                    v.data.bits = sum_bits;
-                }
-            }
-            output->row_count++;
-        }
-        }
-emitted:
-        if (stats) {
-            stats->rows_read = chunk->row_count;
-            stats->rows_written = output->row_count;
-            stats->grouped_row_count = ngroups + (th.side_used[1] ? 1 : 0);
-            stats->incomplete_input = in_clamped;
-            stats->incomplete_output = out_limited || (th.overflow == 2);
-            stats->kernel_scan_ms += ms;
-            stats->kernel_scan_launches += 1;
-            stats->kernel_other_ms += ms_other;   /* compact + result D2H */
-            stats->execute_time_ms = now_ms() - tw0;
-        }
-        g_pool.put(d_accbase); g_pool.put(d_acc); g_pool.put(d_hashes);
-        g_pool.put(d_idents); g_pool.put(d_pfxs);
-        g_pool.put(d_slots); g_pool.put(d_out); g_pool.put(d_pool);
-        g_pool.put(d_ctr); g_pool.put(hgroups);
-        g_pool.put(d_slotaggs); g_pool.put(d_oaggs); g_pool.put(haggs);
+        rc = emit_string_general(plan, sum_type, hgroups, haggs, ngroups,
+                                 pool.data(), th, options->output_row_limit,
+                                 &out_limited, output, errbuf, errlen);
+    } else {
+        rc = emit_string_sums(ps, plan, options, R.stream, d_out, hgroups,
+                              ngroups, d_pool, hctr[1], th, sum_slot,
+                              val_is_double, &out_limited, output, errbuf, errlen);
     }
-    return rc;
-fail:
+    if (stats) {
+        stats->rows_read = chunk->row_count;
+        stats->rows_written = output->row_count;
+        stats->grouped_row_count = ngroups + (th.side_used[1] ? 1 : 0);
+        stats->incomplete_input = in_clamped;
+        stats->incomplete_output = out_limited || (th.overflow == 2);
+        stats->kernel_scan_ms += ms;
+        stats->kernel_scan_launches += 1;
+        stats->kernel_other_ms += ms_other;   /* compact + result D2H */
+        stats->execute_time_ms = now_ms() - tw0;
+    }
     return rc;
 }
 
@@ -4240,52 +4179,43 @@ extern "C" int yt_gpu_versioned_read(
         return YT_ERR_INVALID_CHUNK;
     }
     std::vector<VSegDev> h_segs((size_t)nseg);
-    std::vector<void*> blobs;
+    PoolScope ps;
     int64_t total_rows = 0;
-    {
-        for (int i = 0; i < nseg; i++) {
-            const YtTimestampSeg& T = col->ts_segs[i];
-            const YtVersionedValueSeg& V = col->val_segs[i];
-            char* d_t = nullptr;
-            char* d_v = nullptr;
-            /* +8 pad: bp_gl may read one word past the last vector */
-            HIP_CHECK(pool_alloc(&d_t, (size_t)T.data_size + 8));
-            HIP_CHECK(pool_alloc(&d_v, (size_t)V.data_size + 8));
-            blobs.push_back(d_t);
-            blobs.push_back(d_v);
-            HIP_CHECK(hipMemcpyAsync(d_t, T.data, (size_t)T.data_size,
-                                     hipMemcpyHostToDevice, st));
-            HIP_CHECK(hipMemcpyAsync(d_v, V.data, (size_t)V.data_size,
-                                     hipMemcpyHostToDevice, st));
-            VSegDev& S = h_segs[i];
-            S.row_start = total_rows;
-            S.row_count = T.row_count;
-            S.base_timestamp = T.base_timestamp;
-            S.exp_w = T.expected_writes_per_row;
-            S.exp_d = T.expected_deletes_per_row;
-            S.exp_v = V.expected_values_per_row;
-            S.vtype = V.type;
-            S.vflags = V.flags;
-            S.base_value = V.base_value;
-            S.ts_data = d_t;
-            S.val_data = d_v;
-            total_rows += T.row_count;
-        }
-        VSegDev* d_segs = nullptr;
-        HIP_CHECK(pool_alloc(&d_segs, sizeof(VSegDev) * nseg));
-        blobs.push_back(d_segs);
-        HIP_CHECK(hipMemcpyAsync(d_segs, h_segs.data(), sizeof(VSegDev) * nseg,
+    for (int i = 0; i < nseg; i++) {
+        const YtTimestampSeg& T = col->ts_segs[i];
+        const YtVersionedValueSeg& V = col->val_segs[i];
+        char* d_t = nullptr;
+        char* d_v = nullptr;
+        /* +8 pad: bp_gl may read one word past the last vector */
+        HIP_CHECK(ps.dev(&d_t, (size_t)T.data_size + 8));
+        HIP_CHECK(ps.dev(&d_v, (size_t)V.data_size + 8));
+        HIP_CHECK(hipMemcpyAsync(d_t, T.data, (size_t)T.data_size,
                                  hipMemcpyHostToDevice, st));
-        HIP_CHECK(ytql_launch_versioned_read(d_segs, nseg, total_rows,
-                                             timestamp, out_bits, out_null,
-                                             out_visible, out_agg, st));
-        HIP_CHECK(hipStreamSynchronize(st));
+        HIP_CHECK(hipMemcpyAsync(d_v, V.data, (size_t)V.data_size,
+                                 hipMemcpyHostToDevice, st));
+        VSegDev& S = h_segs[i];
+        S.row_start = total_rows;
+        S.row_count = T.row_count;
+        S.base_timestamp = T.base_timestamp;
+        S.exp_w = T.expected_writes_per_row;
+        S.exp_d = T.expected_deletes_per_row;
+        S.exp_v = V.expected_values_per_row;
+        S.vtype = V.type;
+        S.vflags = V.flags;
+        S.base_value = V.base_value;
+        S.ts_data = d_t;
+        S.val_data = d_v;
+        total_rows += T.row_count;
     }
-    for (void* p : blobs) g_pool.put(p);
+    VSegDev* d_segs = nullptr;
+    HIP_CHECK(ps.dev(&d_segs, sizeof(VSegDev) * nseg));
+    HIP_CHECK(hipMemcpyAsync(d_segs, h_segs.data(), sizeof(VSegDev) * nseg,
+                             hipMemcpyHostToDevice, st));
+    HIP_CHECK(ytql_launch_versioned_read(d_segs, nseg, total_rows,
+                                         timestamp, out_bits, out_null,
+                                         out_visible, out_agg, st));
+    HIP_CHECK(hipStreamSynchronize(st));
     return YT_OK;
-fail:
-    for (void* p : blobs) g_pool.put(p);
-    return rc;
 }
 
 namespace {
@@ -4293,6 +4223,9 @@ struct ScanChunkHandle {
     char* blob = nullptr;              /* device */
     YtSegment* segs = nullptr;         /* host heap */
     YtColumn* col = nullptr;           /* host heap */
+
+    /* the blob is the pool's: yt_gpu_scan_chunk_free puts it back */
+    ~ScanChunkHandle() { free(segs); free(col); }
 };
 } /* namespace */
 
@@ -4366,7 +4299,8 @@ extern "C" int yt_gpu_versioned_scan_table(
     }
     const int ncols = nkey + nvcols;
 
-    auto* H = new ScanChunkHandle();
+    std::unique_ptr<ScanChunkHandle> H(new ScanChunkHandle());
+    PoolScope ps;
     std::vector<uint64_t*> d_bits(ncols, nullptr);
     std::vector<uint8_t*> d_null(ncols, nullptr);
     uint8_t* d_vis = nullptr;
@@ -4377,26 +4311,20 @@ extern "C" int yt_gpu_versioned_scan_table(
     int grid = (int)((n + 255) / 256);
     if (grid > 2048) grid = 2048;
     if (grid < 1) grid = 1;
-    auto cleanup = [&]() {
-        for (auto* p : d_bits) g_pool.put(p);
-        for (auto* p : d_null) g_pool.put(p);
-        g_pool.put(d_vis); g_pool.put(d_vis2);
-        g_pool.put(d_blk); g_pool.put(d_off);
-    };
     std::vector<int> col_is_dbl(ncols, 0);
     std::vector<unsigned long long> blk((size_t)grid);
     std::vector<int64_t> seg_rows, seg_bytes;
     int64_t total = 0, col_bytes = 0, blob_bytes = 0;
     int nseg = 0;
-    if (n == 0) { *out_handle = H; return YT_OK; }
+    if (n == 0) { *out_handle = H.release(); return YT_OK; }
 
     for (int c = 0; c < ncols; c++) {
-        HIP_CHECK(pool_alloc(&d_bits[c], sizeof(uint64_t) * n));
-        HIP_CHECK(pool_alloc(&d_null[c], (size_t)n));
+        HIP_CHECK(ps.dev(&d_bits[c], sizeof(uint64_t) * n));
+        HIP_CHECK(ps.dev(&d_null[c], (size_t)n));
     }
-    HIP_CHECK(pool_alloc(&d_vis, (size_t)n));
-    HIP_CHECK(pool_alloc(&d_vis2, (size_t)n));
-    HIP_CHECK(pool_alloc(&d_blk, sizeof(unsigned long long) * grid));
+    HIP_CHECK(ps.dev(&d_vis, (size_t)n));
+    HIP_CHECK(ps.dev(&d_vis2, (size_t)n));
+    HIP_CHECK(ps.dev(&d_blk, sizeof(unsigned long long) * grid));
 
     /* key columns: decode unversioned DirectDense int64 */
     if (nkey) {
@@ -4405,7 +4333,7 @@ extern "C" int yt_gpu_versioned_scan_table(
         unsigned maxw = 0;
         int clamped = 0;
         rc = setup_chunk(key_chunk, &R2, &maxw, 0, &clamped, errbuf, errlen);
-        if (rc != YT_OK) { cleanup(); delete H; return rc; }
+        if (rc != YT_OK) return rc;
         HIP_CHECK(hipMemsetAsync(R2.d_err, 0, sizeof(unsigned), st));
         for (int c = 0; c < nkey; c++) {
             HIP_CHECK(ytql_launch_unvcol_to_arrays(R2.d_segs, R2.d_segex,
@@ -4417,7 +4345,6 @@ extern "C" int yt_gpu_versioned_scan_table(
         HIP_CHECK(hipMemcpy(&kerr, R2.d_err, sizeof(unsigned), hipMemcpyDeviceToHost));
         if (kerr) {
             set_err(errbuf, errlen, "scan_table: string key columns not bridged this round");
-            cleanup(); delete H;
             return YT_ERR_UNSUPPORTED;
         }
     }
@@ -4432,7 +4359,7 @@ extern "C" int yt_gpu_versioned_scan_table(
         rc = yt_gpu_versioned_read(vc, timestamp, d_bits[nkey + j],
                                    d_null[nkey + j], j == 0 ? d_vis : d_vis2,
                                    nullptr, stream, errbuf, errlen);
-        if (rc != YT_OK) { cleanup(); delete H; return rc; }
+        if (rc != YT_OK) return rc;
     }
 
     HIP_CHECK(ytql_launch_vis_count(d_vis, n, d_blk, grid, st));
@@ -4445,8 +4372,7 @@ extern "C" int yt_gpu_versioned_scan_table(
     }
     nseg = (int)((total + kSegCap - 1) / kSegCap);
     if (total == 0) {
-        cleanup();
-        *out_handle = H;
+        *out_handle = H.release();
         return YT_OK;
     }
     HIP_CHECK(hipMemcpyAsync(d_blk, blk.data(), sizeof(unsigned long long) * grid,
@@ -4462,9 +4388,9 @@ extern "C" int yt_gpu_versioned_scan_table(
         col_bytes += seg_bytes[i];
     }
     blob_bytes = col_bytes * ncols;
-    HIP_CHECK(pool_alloc(&H->blob, (size_t)blob_bytes + 8));
+    HIP_CHECK(ps.dev(&H->blob, (size_t)blob_bytes + 8));
     HIP_CHECK(hipMemsetAsync(H->blob, 0, (size_t)blob_bytes, st));
-    HIP_CHECK(pool_alloc(&d_off, sizeof(int64_t) * nseg));
+    HIP_CHECK(ps.dev(&d_off, sizeof(int64_t) * nseg));
 
     H->segs = (YtSegment*)calloc((size_t)nseg * ncols, sizeof(YtSegment));
     H->col = (YtColumn*)calloc(ncols, sizeof(YtColumn));
@@ -4500,13 +4426,9 @@ extern "C" int yt_gpu_versioned_scan_table(
     out_chunk->row_count = total;
     out_chunk->column_count = ncols;
     out_chunk->columns = H->col;
-    *out_handle = H;
-    cleanup();
+    ps.detach(H->blob);         /* the handle's from here on */
+    *out_handle = H.release();
     return YT_OK;
-fail:
-    cleanup();
-    delete H;
-    return rc;
 }
 
 extern "C" void yt_gpu_scan_chunk_free(YtChunk* chunk, void* handle)
@@ -4514,8 +4436,6 @@ extern "C" void yt_gpu_scan_chunk_free(YtChunk* chunk, void* handle)
     auto* H = (ScanChunkHandle*)handle;
     if (!H) return;
     g_pool.put(H->blob);
-    free(H->segs);
-    free(H->col);
     delete H;
     if (chunk) memset(chunk, 0, sizeof(*chunk));
 }
@@ -4670,21 +4590,30 @@ extern "C" int yt_gpu_query_execute(
 
     /* compact + readback (pinned staging from the pool) */
     TableHdr th;
-    OutGroup* hgroups = nullptr;
-    SlimGroup* hslim = nullptr;
-    SlimSlices slices;
-    slices.count = 0;
-    slices.per = 0;
     int64_t ngroups = 0;
     {
+        /* the staging buffers and slice events live as long as this block;
+         * `drain` is declared after `ps`, so on every way out the stream is
+         * idle before the pool takes the pinned staging back */
+        PoolScope ps;
+        struct Drain {
+            hipStream_t st;
+            bool armed;
+            ~Drain() { if (armed) (void)hipStreamSynchronize(st); }
+        } drain{R.stream, false};
+        OutGroup* hgroups = nullptr;
+        SlimGroup* hslim = nullptr;
+        SlimSlices slices;
+        slices.count = 0;
+        slices.per = 0;
         /* the partitioned path already brought the header back */
         if (R.th_valid) th = *R.h_th;
         else HIP_CHECK(hipMemcpy(&th, R.d_th, sizeof(th), hipMemcpyDeviceToHost));
-        if (th.overflow == 1) { set_err(errbuf, errlen, "group table overflow — raise max_groups_hint"); rc = YT_ERR_CAPACITY; goto fail; }
+        if (th.overflow == 1) { set_err(errbuf, errlen, "group table overflow — raise max_groups_hint"); return YT_ERR_CAPACITY; }
         ngroups = (int64_t)th.ngroups;
         if (ngroups > 0 && !R.groups_compacted) {
-            HIP_CHECK(pool_alloc(&R.d_groups, sizeof(OutGroup) * ngroups));
-            HIP_CHECK(pool_alloc(&R.d_counter, sizeof(unsigned long long)));
+            HIP_CHECK(R.ps.dev(&R.d_groups, sizeof(OutGroup) * ngroups));
+            HIP_CHECK(R.ps.dev(&R.d_counter, sizeof(unsigned long long)));
             HIP_CHECK(hipMemsetAsync(R.d_counter, 0, sizeof(unsigned long long), R.stream));
             HIP_CHECK(ytql_launch_compact(nullptr, R.d_th, R.d_slots, plan->agg_count,
                                           R.d_groups, R.d_counter, R.nslots, R.stream));
@@ -4694,7 +4623,8 @@ extern "C" int yt_gpu_query_execute(
              * run its workers) in slices, so that the emit of one slice
              * overlaps the copy of the next */
             const SlimGroup* d_slim = (const SlimGroup*)R.d_groups;
-            HIP_CHECK(pool_alloc_host(&hslim, sizeof(SlimGroup) * ngroups));
+            HIP_CHECK(ps.host(&hslim, sizeof(SlimGroup) * ngroups));
+            drain.armed = true;
             const int want = ngroups >= 65536 ? kGroupSlices : 1;
             slices.per = (ngroups + want - 1) / want;
             for (int64_t a = 0; a < ngroups; a += slices.per) {
@@ -4702,19 +4632,18 @@ extern "C" int yt_gpu_query_execute(
                 HIP_CHECK(hipMemcpyAsync(hslim + a, d_slim + a, sizeof(SlimGroup) * cnt,
                                          hipMemcpyDeviceToHost, R.stream));
                 hipEvent_t ev = nullptr;
-                HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+                HIP_CHECK(ps.event(&ev, hipEventDisableTiming));
                 slices.ev[slices.count++] = ev;
                 HIP_CHECK(hipEventRecord(ev, R.stream));
             }
         } else if (ngroups > 0) {
-            HIP_CHECK(pool_alloc_host(&hgroups, sizeof(OutGroup) * ngroups));
+            HIP_CHECK(ps.host(&hgroups, sizeof(OutGroup) * ngroups));
+            drain.armed = true;
             HIP_CHECK(hipMemcpyAsync(hgroups, R.d_groups, sizeof(OutGroup) * ngroups,
                                      hipMemcpyDeviceToHost, R.stream));
             HIP_CHECK(hipStreamSynchronize(R.stream));
         }
-    }
-    tp2 = now_ms();
-    {
+        tp2 = now_ms();
         std::vector<uint64_t> gaccum(1 + 2 * kMaxAggs, 0);
         if (fs.valid && fs.key_col < 0) {
             HIP_CHECK(hipMemcpy(gaccum.data(), R.d_gaccum,
@@ -4726,20 +4655,14 @@ extern "C" int yt_gpu_query_execute(
                        options->output_row_limit, &out_limited,
                        output, errbuf, errlen, hslim, hslim ? &slices : nullptr);
         if (hslim) {
-            /* nothing may still be writing the staging buffer when the pool
-             * takes it back (emit_rows can return before the last slice) */
+            /* emit_rows can return before the last slice has landed */
             hipError_t es = hipStreamSynchronize(R.stream);
             if (es != hipSuccess && rc == YT_OK) {
                 set_err(errbuf, errlen, hipGetErrorString(es));
                 rc = YT_ERR_HIP;
             }
         }
-        for (int i = 0; i < slices.count; i++) (void)hipEventDestroy(slices.ev[i]);
-        slices.count = 0;
-        g_pool.put(hgroups);
-        g_pool.put(hslim);
-        hgroups = nullptr;
-        hslim = nullptr;
+        drain.armed = false;
         if (rc) return rc;
         if (out_limited && stats) stats->incomplete_output = 1;
     }
@@ -4772,12 +4695,6 @@ extern "C" int yt_gpu_query_execute(
         stats->execute_time_ms = now_ms() - tw0;
     }
     return YT_OK;
-fail:
-    if (hslim || hgroups) (void)hipStreamSynchronize(R.stream);
-    for (int i = 0; i < slices.count; i++) (void)hipEventDestroy(slices.ev[i]);
-    g_pool.put(hgroups);
-    g_pool.put(hslim);
-    return rc;
 }
 
 static int query_partial_impl(
@@ -4893,94 +4810,87 @@ static int query_partial_impl(
 
     TableHdr th;
     double tq15 = now_ms();
-    {
-        HIP_CHECK(hipMemcpy(&th, R.d_th, sizeof(th), hipMemcpyDeviceToHost));
-        if (th.overflow == 1) { set_err(errbuf, errlen, "group table overflow"); rc = YT_ERR_CAPACITY; goto fail; }
-        int64_t ngroups = (int64_t)th.ngroups;
-        int64_t total = ngroups + th.side_used[0] + th.side_used[1];
-        if (total > capacity_rows) { set_err(errbuf, errlen, "state buffer too small"); rc = YT_ERR_CAPACITY; goto fail; }
+    HIP_CHECK(hipMemcpy(&th, R.d_th, sizeof(th), hipMemcpyDeviceToHost));
+    if (th.overflow == 1) { set_err(errbuf, errlen, "group table overflow"); return YT_ERR_CAPACITY; }
+    int64_t ngroups = (int64_t)th.ngroups;
+    int64_t total = ngroups + th.side_used[0] + th.side_used[1];
+    if (total > capacity_rows) { set_err(errbuf, errlen, "state buffer too small"); return YT_ERR_CAPACITY; }
 
-        if (!R.groups_compacted) {
-            /* compact table into OutGroups (device) */
-            HIP_CHECK(pool_alloc(&R.d_groups, sizeof(OutGroup) * (total ? total : 1)));
-            HIP_CHECK(pool_alloc(&R.d_counter, sizeof(unsigned long long)));
-            HIP_CHECK(hipMemsetAsync(R.d_counter, 0, sizeof(unsigned long long), R.stream));
-            if (ngroups > 0) {
-                HIP_CHECK(ytql_launch_compact(nullptr, R.d_th, R.d_slots, plan->agg_count,
-                                              R.d_groups, R.d_counter, R.nslots, R.stream));
-            }
-        } else if (R.groups_capacity < total) {
-            set_err(errbuf, errlen, "state buffer too small");
-            rc = YT_ERR_CAPACITY;
-            goto fail;
+    if (!R.groups_compacted) {
+        /* compact table into OutGroups (device) */
+        HIP_CHECK(R.ps.dev(&R.d_groups, sizeof(OutGroup) * (total ? total : 1)));
+        HIP_CHECK(R.ps.dev(&R.d_counter, sizeof(unsigned long long)));
+        HIP_CHECK(hipMemsetAsync(R.d_counter, 0, sizeof(unsigned long long), R.stream));
+        if (ngroups > 0) {
+            HIP_CHECK(ytql_launch_compact(nullptr, R.d_th, R.d_slots, plan->agg_count,
+                                          R.d_groups, R.d_counter, R.nslots, R.stream));
         }
-        /* append side groups from host */
-        int64_t pos = ngroups;
-        for (int side = 0; side < 2; side++) {
-            if (!th.side_used[side]) continue;
-            OutGroup g;
-            memset(&g, 0, sizeof(g));
-            g.key_bits = th.side_key_bits[side];
-            g.key_meta = (side == 1);
-            g.cnt = th.side_cnt[side];
-            for (int a = 0; a < plan->agg_count; a++) {
-                g.agg_bits[a] = th.side_agg[side][2 * a];
-                g.agg_nonnull[a] = th.side_agg[side][2 * a + 1];
-            }
-            HIP_CHECK(hipMemcpyAsync(R.d_groups + pos, &g, sizeof(g),
-                                     hipMemcpyHostToDevice, R.stream));
-            pos++;
+    } else if (R.groups_capacity < total) {
+        set_err(errbuf, errlen, "state buffer too small");
+        return YT_ERR_CAPACITY;
+    }
+    /* append side groups from host */
+    int64_t pos = ngroups;
+    for (int side = 0; side < 2; side++) {
+        if (!th.side_used[side]) continue;
+        OutGroup g;
+        memset(&g, 0, sizeof(g));
+        g.key_bits = th.side_key_bits[side];
+        g.key_meta = (side == 1);
+        g.cnt = th.side_cnt[side];
+        for (int a = 0; a < plan->agg_count; a++) {
+            g.agg_bits[a] = th.side_agg[side][2 * a];
+            g.agg_nonnull[a] = th.side_agg[side][2 * a + 1];
         }
-
-        /* partition counts → host prefix → scatter */
-        double tq2 = now_ms();
-        unsigned long long* d_counts = nullptr;
-        HIP_CHECK(pool_alloc(&d_counts, sizeof(unsigned long long) * partition_count));
-        HIP_CHECK(hipMemsetAsync(d_counts, 0, sizeof(unsigned long long) * partition_count, R.stream));
-        HIP_CHECK(ytql_launch_part_count(R.d_groups, total, partition_count, sum_slot,
-                                         d_counts, R.stream));
-        std::vector<unsigned long long> counts(partition_count);
-        HIP_CHECK(hipMemcpyAsync(counts.data(), d_counts,
-                                 sizeof(unsigned long long) * partition_count,
-                                 hipMemcpyDeviceToHost, R.stream));
-        HIP_CHECK(hipStreamSynchronize(R.stream));
-        std::vector<unsigned long long> cursors(partition_count);
-        unsigned long long run = 0;
-        for (int p = 0; p < partition_count; p++) { cursors[p] = run; run += counts[p]; }
-        HIP_CHECK(hipMemcpyAsync(d_counts, cursors.data(),
-                                 sizeof(unsigned long long) * partition_count,
+        HIP_CHECK(hipMemcpyAsync(R.d_groups + pos, &g, sizeof(g),
                                  hipMemcpyHostToDevice, R.stream));
-        int sum_is_double = 0;
-        if (sum_slot >= 0) {
-            /* dp.col_types already appends the joined foreign columns */
-            int at = expr_static_type(plan->aggs[sum_slot]->arg, dp.col_types);
-            sum_is_double = at == YT_VT_DOUBLE;
-            if ((state_func == YT_AGG_MIN || state_func == YT_AGG_MAX) &&
-                at != YT_VT_INT64 && at != YT_VT_DOUBLE) {
-                set_err(errbuf, errlen,
-                        "partial: min/max over int64/double args this round");
-                rc = YT_ERR_UNSUPPORTED;
-                goto fail;
-            }
-        }
-        HIP_CHECK(ytql_launch_part_scatter(R.d_groups, total, partition_count, sum_slot,
-                                           sum_is_double, state_func,
-                                           d_counts, (YtStateRow*)states_device, R.stream));
-        HIP_CHECK(hipStreamSynchronize(R.stream));
-        g_pool.put(d_counts);
-        for (int p = 0; p < partition_count; p++) part_counts[p] = (int64_t)counts[p];
-        if (getenv("YTQL_TIMING"))
-            fprintf(stderr, "[ytql timing] partial total %.2fms (compact+sides %.2fms count/scatter %.2fms)\n",
-                    now_ms() - tw0, tq2 - tq15, now_ms() - tq2);
-        if (stats) {
-            stats->rows_read = chunk->row_count;
-            stats->grouped_row_count = total;
-            stats->incomplete_output = (th.overflow == 2);
+        pos++;
+    }
+
+    /* partition counts → host prefix → scatter */
+    double tq2 = now_ms();
+    unsigned long long* d_counts = nullptr;
+    HIP_CHECK(R.ps.dev(&d_counts, sizeof(unsigned long long) * partition_count));
+    HIP_CHECK(hipMemsetAsync(d_counts, 0, sizeof(unsigned long long) * partition_count, R.stream));
+    HIP_CHECK(ytql_launch_part_count(R.d_groups, total, partition_count, sum_slot,
+                                     d_counts, R.stream));
+    std::vector<unsigned long long> counts(partition_count);
+    HIP_CHECK(hipMemcpyAsync(counts.data(), d_counts,
+                             sizeof(unsigned long long) * partition_count,
+                             hipMemcpyDeviceToHost, R.stream));
+    HIP_CHECK(hipStreamSynchronize(R.stream));
+    std::vector<unsigned long long> cursors(partition_count);
+    unsigned long long run = 0;
+    for (int p = 0; p < partition_count; p++) { cursors[p] = run; run += counts[p]; }
+    HIP_CHECK(hipMemcpyAsync(d_counts, cursors.data(),
+                             sizeof(unsigned long long) * partition_count,
+                             hipMemcpyHostToDevice, R.stream));
+    int sum_is_double = 0;
+    if (sum_slot >= 0) {
+        /* dp.col_types already appends the joined foreign columns */
+        int at = expr_static_type(plan->aggs[sum_slot]->arg, dp.col_types);
+        sum_is_double = at == YT_VT_DOUBLE;
+        if ((state_func == YT_AGG_MIN || state_func == YT_AGG_MAX) &&
+            at != YT_VT_INT64 && at != YT_VT_DOUBLE) {
+            set_err(errbuf, errlen,
+                    "partial: min/max over int64/double args this round");
+            return YT_ERR_UNSUPPORTED;
         }
     }
+    HIP_CHECK(ytql_launch_part_scatter(R.d_groups, total, partition_count, sum_slot,
+                                       sum_is_double, state_func,
+                                       d_counts, (YtStateRow*)states_device, R.stream));
+    HIP_CHECK(hipStreamSynchronize(R.stream));
+    for (int p = 0; p < partition_count; p++) part_counts[p] = (int64_t)counts[p];
+    if (getenv("YTQL_TIMING"))
+        fprintf(stderr, "[ytql timing] partial total %.2fms (compact+sides %.2fms count/scatter %.2fms)\n",
+                now_ms() - tw0, tq2 - tq15, now_ms() - tq2);
+    if (stats) {
+        stats->rows_read = chunk->row_count;
+        stats->grouped_row_count = total;
+        stats->incomplete_output = (th.overflow == 2);
+    }
     return YT_OK;
-fail:
-    return rc;
 }
 
 extern "C" int yt_gpu_query_partial(
@@ -5130,89 +5040,83 @@ static int merge_states_impl(
     if (getenv("YTQL_TIMING"))
         fprintf(stderr, "[ytql timing] merge: setup %.2fms kernel %.2fms\n",
                 tq1 - tw0, now_ms() - tq1);
-    {
-        TableHdr th;
-        HIP_CHECK(hipMemcpy(&th, R.d_th, sizeof(th), hipMemcpyDeviceToHost));
-        if (th.overflow == 1) { set_err(errbuf, errlen, "merge table overflow"); rc = YT_ERR_CAPACITY; goto fail; }
-        int64_t ngroups = (int64_t)th.ngroups;
-        OutGroup* hgroups = nullptr;
-        if (ngroups > 0) {
-            HIP_CHECK(pool_alloc(&R.d_groups, sizeof(OutGroup) * ngroups));
-            HIP_CHECK(pool_alloc(&R.d_counter, sizeof(unsigned long long)));
-            HIP_CHECK(hipMemsetAsync(R.d_counter, 0, sizeof(unsigned long long), R.stream));
-            HIP_CHECK(ytql_launch_compact(nullptr, R.d_th, R.d_slots, plan->agg_count,
-                                          R.d_groups, R.d_counter, R.nslots, R.stream));
-            HIP_CHECK(pool_alloc_host(&hgroups, sizeof(OutGroup) * ngroups));
-            HIP_CHECK(hipMemcpyAsync(hgroups, R.d_groups, sizeof(OutGroup) * ngroups,
-                                     hipMemcpyDeviceToHost, R.stream));
-            HIP_CHECK(hipStreamSynchronize(R.stream));
-        }
-        /* fabricate a single-int64-column chunk view for type inference:
-         * the key static type is carried by plan->keys[0] over col types.
-         * Merge callers use the same chunk schema as partial; we only need
-         * col_types for expr_static_type — rebuild from the key expr columns
-         * is not possible here, so default key/sum types to int64. */
-        YtColumn col;
-        memset(&col, 0, sizeof(col));
-        col.value_type = YT_VT_INT64;
-        col.segment_count = 0;
-        std::vector<YtColumn> cols(kMaxCols, col);
-        if (col_types) {
-            for (int c2 = 0; c2 < kMaxCols; c2++)
-                cols[c2].value_type = col_types[c2];
-        }
-        YtChunk fake;
-        fake.row_count = 0;
-        fake.column_count = kMaxCols;
-        fake.columns = cols.data();
-        /* multi-key: rebuild the composite packing from the COMMON ranges
-         * (identical math to every rank's partial — pack_group_key) so
-         * emit unpacks the key components */
-        DevPlan dpk;
-        DevPlan* dpk_p = nullptr;
-        if (plan->key_count > 1) {
-            memset(&dpk, 0, sizeof(dpk));
-            dpk.ncols = kMaxCols;
-            for (int c2 = 0; c2 < kMaxCols; c2++)
-                dpk.col_types[c2] = col_types ? col_types[c2] : YT_VT_INT64;
-            dpk.kp_count = plan->key_count;
-            DeviceRun R2;   /* host-side ranges only */
-            for (int i = 0; i < plan->key_count; i++) {
-                int c2;
-                if (!expr_is_col(plan->keys[i], &c2) || c2 >= kMaxCols) {
-                    set_err(errbuf, errlen, "merge: plain key columns only");
-                    g_pool.put(hgroups);
-                    return YT_ERR_UNSUPPORTED;
-                }
-                dpk.kp_col[i] = c2;
-                dpk.kp_signed[i] = dpk.col_types[c2] == YT_VT_INT64;
-                R2.col_zzmin[c2] = key_zzmin[i];
-                R2.col_zzmax[c2] = key_zzmax[i];
+    TableHdr th;
+    HIP_CHECK(hipMemcpy(&th, R.d_th, sizeof(th), hipMemcpyDeviceToHost));
+    if (th.overflow == 1) { set_err(errbuf, errlen, "merge table overflow"); return YT_ERR_CAPACITY; }
+    int64_t ngroups = (int64_t)th.ngroups;
+    OutGroup* hgroups = nullptr;
+    if (ngroups > 0) {
+        HIP_CHECK(R.ps.dev(&R.d_groups, sizeof(OutGroup) * ngroups));
+        HIP_CHECK(R.ps.dev(&R.d_counter, sizeof(unsigned long long)));
+        HIP_CHECK(hipMemsetAsync(R.d_counter, 0, sizeof(unsigned long long), R.stream));
+        HIP_CHECK(ytql_launch_compact(nullptr, R.d_th, R.d_slots, plan->agg_count,
+                                      R.d_groups, R.d_counter, R.nslots, R.stream));
+        HIP_CHECK(R.ps.host(&hgroups, sizeof(OutGroup) * ngroups));
+        HIP_CHECK(hipMemcpyAsync(hgroups, R.d_groups, sizeof(OutGroup) * ngroups,
+                                 hipMemcpyDeviceToHost, R.stream));
+        HIP_CHECK(hipStreamSynchronize(R.stream));
+    }
+    /* fabricate a single-int64-column chunk view for type inference:
+     * the key static type is carried by plan->keys[0] over col types.
+     * Merge callers use the same chunk schema as partial; we only need
+     * col_types for expr_static_type — rebuild from the key expr columns
+     * is not possible here, so default key/sum types to int64. */
+    YtColumn col;
+    memset(&col, 0, sizeof(col));
+    col.value_type = YT_VT_INT64;
+    col.segment_count = 0;
+    std::vector<YtColumn> cols(kMaxCols, col);
+    if (col_types) {
+        for (int c2 = 0; c2 < kMaxCols; c2++)
+            cols[c2].value_type = col_types[c2];
+    }
+    YtChunk fake;
+    fake.row_count = 0;
+    fake.column_count = kMaxCols;
+    fake.columns = cols.data();
+    /* multi-key: rebuild the composite packing from the COMMON ranges
+     * (identical math to every rank's partial — pack_group_key) so
+     * emit unpacks the key components */
+    DevPlan dpk;
+    DevPlan* dpk_p = nullptr;
+    if (plan->key_count > 1) {
+        memset(&dpk, 0, sizeof(dpk));
+        dpk.ncols = kMaxCols;
+        for (int c2 = 0; c2 < kMaxCols; c2++)
+            dpk.col_types[c2] = col_types ? col_types[c2] : YT_VT_INT64;
+        dpk.kp_count = plan->key_count;
+        DeviceRun R2;   /* host-side ranges only */
+        for (int i = 0; i < plan->key_count; i++) {
+            int c2;
+            if (!expr_is_col(plan->keys[i], &c2) || c2 >= kMaxCols) {
+                set_err(errbuf, errlen, "merge: plain key columns only");
+                return YT_ERR_UNSUPPORTED;
             }
-            rc = pack_group_key(&dpk, &R2, errbuf, errlen);
-            if (rc) { g_pool.put(hgroups); return rc; }
-            dpk_p = &dpk;
+            dpk.kp_col[i] = c2;
+            dpk.kp_signed[i] = dpk.col_types[c2] == YT_VT_INT64;
+            R2.col_zzmin[c2] = key_zzmin[i];
+            R2.col_zzmax[c2] = key_zzmax[i];
         }
-        int out_limited = 0;
-        rc = emit_rows(plan, &fake, dpk_p, hgroups, ngroups, th, 0,
-                       nullptr, 0, options->output_row_limit, &out_limited,
-                       output, errbuf, errlen);
-        g_pool.put(hgroups);
+        rc = pack_group_key(&dpk, &R2, errbuf, errlen);
         if (rc) return rc;
-        if (out_limited && stats) stats->incomplete_output = 1;
-        if (plan->order_count > 0 || plan->with_totals || plan->having) {
-            /* ORDER BY / WITH TOTALS / HAVING apply at the front query */
-            rc = finish_output(plan, output, errbuf, errlen);
-            if (rc) return rc;
-        }
-        if (stats) {
-            stats->rows_written = output->row_count;
-            stats->grouped_row_count = ngroups + th.side_used[0] + th.side_used[1];
-        }
+        dpk_p = &dpk;
+    }
+    int out_limited = 0;
+    rc = emit_rows(plan, &fake, dpk_p, hgroups, ngroups, th, 0,
+                   nullptr, 0, options->output_row_limit, &out_limited,
+                   output, errbuf, errlen);
+    if (rc) return rc;
+    if (out_limited && stats) stats->incomplete_output = 1;
+    if (plan->order_count > 0 || plan->with_totals || plan->having) {
+        /* ORDER BY / WITH TOTALS / HAVING apply at the front query */
+        rc = finish_output(plan, output, errbuf, errlen);
+        if (rc) return rc;
+    }
+    if (stats) {
+        stats->rows_written = output->row_count;
+        stats->grouped_row_count = ngroups + th.side_used[0] + th.side_used[1];
     }
     return YT_OK;
-fail:
-    return rc;
 }
 
 extern "C" int yt_gpu_merge_states(
@@ -5315,26 +5219,19 @@ extern "C" int yt_gpu_merge_states_str(
     unsigned long long* d_ctr = nullptr;
     OutStrState* hgroups = nullptr;
     char* hpool = nullptr;
-    auto putall = [&]() {
-        g_pool.put(d_rowb); g_pool.put(d_poolb); g_pool.put(d_hashes);
-        g_pool.put(d_idents); g_pool.put(d_pfxs); g_pool.put(d_absoff);
-        g_pool.put(d_slots); g_pool.put(d_th); g_pool.put(d_out);
-        g_pool.put(d_opool); g_pool.put(d_ctr); g_pool.put(hgroups);
-        g_pool.put(hpool);
-    };
-    {
-    HIP_CHECK(pool_alloc(&d_rowb, sizeof(int64_t) * nseg_in));
-    HIP_CHECK(pool_alloc(&d_poolb, sizeof(unsigned long long) * nseg_in));
+    PoolScope ps;
+    HIP_CHECK(ps.dev(&d_rowb, sizeof(int64_t) * nseg_in));
+    HIP_CHECK(ps.dev(&d_poolb, sizeof(unsigned long long) * nseg_in));
     HIP_CHECK(hipMemcpyAsync(d_rowb, row_base.data(),
                              sizeof(int64_t) * nseg_in,
                              hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(d_poolb, pool_base.data(),
                              sizeof(unsigned long long) * nseg_in,
                              hipMemcpyHostToDevice, st));
-    HIP_CHECK(pool_alloc(&d_hashes, sizeof(uint64_t) * n));
-    HIP_CHECK(pool_alloc(&d_idents, sizeof(uint64_t) * n));
-    HIP_CHECK(pool_alloc(&d_pfxs, sizeof(ulonglong2) * n));
-    HIP_CHECK(pool_alloc(&d_absoff, sizeof(uint64_t) * n));
+    HIP_CHECK(ps.dev(&d_hashes, sizeof(uint64_t) * n));
+    HIP_CHECK(ps.dev(&d_idents, sizeof(uint64_t) * n));
+    HIP_CHECK(ps.dev(&d_pfxs, sizeof(ulonglong2) * n));
+    HIP_CHECK(ps.dev(&d_absoff, sizeof(uint64_t) * n));
     uint64_t nslots_cap = next_pow2((uint64_t)n * 2);
     if (nslots_cap < 2048) nslots_cap = 2048;
     uint64_t nslots = options->max_groups_hint > 0
@@ -5342,14 +5239,14 @@ extern "C" int yt_gpu_merge_states_str(
         : nslots_cap;
     if (nslots < 2048) nslots = 2048;
     if (nslots > nslots_cap) nslots = nslots_cap;
-    HIP_CHECK(pool_alloc(&d_th, sizeof(TableHdr)));
+    HIP_CHECK(ps.dev(&d_th, sizeof(TableHdr)));
     HIP_CHECK(ytql_launch_strst_hash((const YtStateRow*)states_device, n,
                                      d_rowb, d_poolb, nseg_in,
                                      (const char*)pool_device,
                                      d_hashes, d_idents, d_pfxs, d_absoff, st));
     TableHdr th;
     for (;;) {
-        HIP_CHECK(pool_alloc(&d_slots, sizeof(StrSlot) * nslots));
+        HIP_CHECK(ps.dev(&d_slots, sizeof(StrSlot) * nslots));
         HIP_CHECK(hipMemsetAsync(d_slots, 0, sizeof(StrSlot) * nslots, st));
         memset(&th, 0, sizeof(th));
         th.group_limit = options->group_row_limit;
@@ -5361,27 +5258,25 @@ extern "C" int yt_gpu_merge_states_str(
                                           d_slots, nslots, d_th, st));
         HIP_CHECK(hipMemcpy(&th, d_th, sizeof(th), hipMemcpyDeviceToHost));
         if (th.overflow != 1 || nslots >= nslots_cap) break;
-        g_pool.put(d_slots);
+        ps.release(d_slots);
         d_slots = nullptr;
         nslots *= 4;
         if (nslots > nslots_cap) nslots = nslots_cap;
     }
     if (th.overflow == 1) {
-        putall();
         set_err(errbuf, errlen, "merge_str: table overflow");
         return YT_ERR_CAPACITY;
     }
     int64_t ngroups = (int64_t)th.ngroups;
     int has_null = th.side_used[1] ? 1 : 0;
     if (ngroups + has_null > output->capacity_rows) {
-        putall();
         set_err(errbuf, errlen, "merge_str: output rowset too small");
         return YT_ERR_CAPACITY;
     }
     uint64_t opool_cap = (uint64_t)(pool_total ? pool_total : 1);
-    HIP_CHECK(pool_alloc(&d_out, sizeof(OutStrState) * (ngroups ? ngroups : 1)));
-    HIP_CHECK(pool_alloc(&d_opool, opool_cap));
-    HIP_CHECK(pool_alloc(&d_ctr, 2 * sizeof(unsigned long long)));
+    HIP_CHECK(ps.dev(&d_out, sizeof(OutStrState) * (ngroups ? ngroups : 1)));
+    HIP_CHECK(ps.dev(&d_opool, opool_cap));
+    HIP_CHECK(ps.dev(&d_ctr, 2 * sizeof(unsigned long long)));
     HIP_CHECK(hipMemsetAsync(d_ctr, 0, 2 * sizeof(unsigned long long), st));
     if (ngroups > 0) {
         HIP_CHECK(ytql_launch_strst_compact(d_slots, nslots, d_absoff,
@@ -5390,7 +5285,7 @@ extern "C" int yt_gpu_merge_states_str(
                                             opool_cap, d_th, st));
     }
     unsigned long long hctr[2] = {0, 0};
-    HIP_CHECK(pool_alloc_host(&hgroups,
+    HIP_CHECK(ps.host(&hgroups,
                               sizeof(OutStrState) * (ngroups ? ngroups : 1)));
     if (ngroups > 0) {
         HIP_CHECK(hipMemcpyAsync(hgroups, d_out,
@@ -5402,33 +5297,15 @@ extern "C" int yt_gpu_merge_states_str(
     HIP_CHECK(hipStreamSynchronize(st));
     if ((unsigned long long)hctr[1] > (unsigned long long)output->string_pool_capacity
         || (output->string_pool == nullptr && hctr[1] != 0)) {
-        putall();
         set_err(errbuf, errlen, "merge_str: string pool too small");
         return YT_ERR_CAPACITY;
     }
     if (hctr[1]) {
-        HIP_CHECK(pool_alloc_host(&hpool, hctr[1]));
+        HIP_CHECK(ps.host(&hpool, hctr[1]));
         HIP_CHECK(hipMemcpyAsync(hpool, d_opool, hctr[1],
                                  hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
-        size_t total_b = (size_t)hctr[1];
-        int ct = (int)std::min<size_t>(std::thread::hardware_concurrency(),
-                                       (total_b + (64 << 20) - 1) / (64 << 20));
-        if (ct > 1) {
-            std::vector<std::thread> cth;
-            size_t per = (total_b + ct - 1) / ct;
-            for (int t2 = 0; t2 < ct; t2++) {
-                size_t b = (size_t)t2 * per;
-                size_t e = std::min(total_b, b + per);
-                if (b >= e) break;
-                cth.emplace_back([&, b, e] {
-                    memcpy(output->string_pool + b, hpool + b, e - b);
-                });
-            }
-            for (auto& th2 : cth) th2.join();
-        } else {
-            memcpy(output->string_pool, hpool, total_b);
-        }
+        copy_parallel(output->string_pool, hpool, (size_t)hctr[1]);
     }
     output->string_pool_used = hctr[1];
     int ncols = 1 + plan->agg_count;
@@ -5438,72 +5315,32 @@ extern "C" int yt_gpu_merge_states_str(
     auto emit_range = [&](int64_t b, int64_t e) {
         for (int64_t g = b; g < e; g++) {
             const OutStrState& gg = hgroups[g];
-            YtValue* dst = output->values + g * ncols;
-            dst[0].id = 0;
-            dst[0].flags = 0;
-            dst[0].type = YT_VT_STRING;
-            dst[0].length = (uint32_t)(gg.off_len & 0xFFFFFF);
-            dst[0].data.str = output->string_pool + (gg.off_len >> 24);
-            for (int a = 0; a < plan->agg_count; a++) {
-                YtValue& v = dst[1 + a];
-                v.id = (uint16_t)(1 + a);
-                v.flags = 0;
-                v.length = 0;
-                if (agg_is_sum1[a]) {
-                    v.type = YT_VT_INT64;
-                    v.data.bits = gg.cnt;
-                } else if (gg.nonnull == 0) {
-                    v.type = YT_VT_NULL;
-                    v.data.bits = 0;
-                } else {
-                    v.type = sum_is_double ? YT_VT_DOUBLE : YT_VT_INT64;
-                    v.data.bits = gg.sum_bits;
-                }
-            }
+            write_str_sum_row(output->values + g * ncols, plan->agg_count,
+                              YT_VT_STRING, (uint32_t)(gg.off_len & 0xFFFFFF),
+                              output->string_pool + (gg.off_len >> 24),
+                              gg.cnt, gg.nonnull, gg.sum_bits,
+                              agg_is_sum1, sum_is_double);
         }
     };
     if (ngroups >= 65536) {
         int nt = (int)std::min<int64_t>(std::thread::hardware_concurrency(),
                                         (ngroups + 65535) / 65536);
-        std::vector<std::thread> ths;
+        ThreadJoiner tj;
         int64_t per = (ngroups + nt - 1) / nt;
         for (int t2 = 0; t2 < nt; t2++) {
             int64_t b = (int64_t)t2 * per;
             int64_t e = std::min<int64_t>(ngroups, b + per);
             if (b >= e) break;
-            ths.emplace_back(emit_range, b, e);
+            tj.ths.emplace_back(emit_range, b, e);
         }
-        for (auto& th2 : ths) th2.join();
     } else {
         emit_range(0, ngroups);
     }
     output->row_count = ngroups;
     if (has_null) {
-        YtValue* dst = output->values + output->row_count * ncols;
-        uint64_t cnt = th.side_cnt[1];
-        uint64_t sum_bits = sum_slot >= 0 ? th.side_agg[1][2 * sum_slot] : 0;
-        uint64_t nonnull = sum_slot >= 0 ? th.side_agg[1][2 * sum_slot + 1] : 0;
-        dst[0].id = 0;
-        dst[0].flags = 0;
-        dst[0].type = YT_VT_NULL;
-        dst[0].length = 0;
-        dst[0].data.bits = 0;
-        for (int a = 0; a < plan->agg_count; a++) {
-            YtValue& v = dst[1 + a];
-            v.id = (uint16_t)(1 + a);
-            v.flags = 0;
-            v.length = 0;
-            if (agg_is_sum1[a]) {
-                v.type = YT_VT_INT64;
-                v.data.bits = cnt;
-            } else if (nonnull == 0) {
-                v.type = YT_VT_NULL;
-                v.data.bits = 0;
-            } else {
-                v.type = sum_is_double ? YT_VT_DOUBLE : YT_VT_INT64;
-                v.data.bits = sum_bits;
-            }
-        }
+        write_str_sum_null_row(output->values + output->row_count * ncols,
+                               plan->agg_count, th, sum_slot, agg_is_sum1,
+                               sum_is_double);
         output->row_count++;
     }
     if (stats) {
@@ -5512,10 +5349,5 @@ extern "C" int yt_gpu_merge_states_str(
         stats->incomplete_output = (th.overflow == 2);
         stats->execute_time_ms = now_ms() - tw0;
     }
-    putall();
     return YT_OK;
-    }
-fail:
-    putall();
-    return rc;
 }
