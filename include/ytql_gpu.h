@@ -117,6 +117,7 @@ enum {
     YT_EX_IS_SUBSTR = 41, /* is_substr(a = literal pattern, b = column) */
     YT_EX_LIKE = 42,      /* a = column LIKE b = literal pattern; lit_i64 =
                              escape byte 0..255, or -1 for none */
+    YT_EX_IN = 43,        /* a IN (list[0 .. list_len)); b unused */
 };
 
 /* String predicates (GPU entries; plan->filter only, anywhere inside its
@@ -138,6 +139,39 @@ enum {
  * and HAVING, string literals and predicates inside a projection, string
  * predicates beside a join, and more than 4 string predicates in one filter.
  * The CPU oracle does not know these nodes. */
+
+/* IN lists (GPU entries): YT_EX_IN with a = the operand and list / list_len =
+ * the literal values (the words of lit_str / lit_len under a second name, so
+ * YtExpr keeps its size); b is unused. This is the reference's TInExpression:
+ * the operand is looked up in the literal rowset with the ROW comparer, the
+ * one joins and group keys use, where null equals null. The contract:
+ *   - the result is a NON-NULL boolean for every row, true iff the operand
+ *     equals one of the listed values;
+ *   - a null operand matches a null literal: null IN (1, 2) is false,
+ *     null IN (1, null) is true;
+ *   - NOT (x IN ...) is YT_EX_NOT over that boolean, so it is never null;
+ *   - duplicates in the list are allowed and mean nothing;
+ *   - the empty list (list_len == 0) is false for every row;
+ *   - strings compare byte-wise, on length and bytes; the empty string is a
+ *     value like any other.
+ * Numeric form: the operand is any expression of static type INT64, UINT64
+ * or BOOLEAN (a plain column, arithmetic, a foreign column beside a join);
+ * every list value has exactly that type or is YT_VT_NULL, anything else is
+ * YT_ERR_INVALID_PLAN "type mismatch". It is allowed wherever an expression
+ * runs on the device (filter, key expression, aggregate argument, projection
+ * of a plain scan) and in HAVING. At most 4 such lists per plan.
+ * String form: the operand is exactly YT_EX_COLUMN over a STRING column of
+ * the primary chunk, the list values are YT_VT_STRING {length, data.str} or
+ * YT_VT_NULL; the bytes stay alive for the call. It is a string predicate:
+ * allowed at any leaf of the filter's AND/OR/NOT tree and nowhere else, not
+ * beside a join, and it takes one of the filter's 4 string-predicate bitmaps
+ * (none when the list holds nothing but nulls).
+ * A list holds at most 1,048,576 values after duplicates are removed; a
+ * longer one is YT_ERR_UNSUPPORTED. Also refused with YT_ERR_UNSUPPORTED:
+ * tuple operands ((a, b) IN ...), a DOUBLE operand, a string operand that is
+ * not a plain primary-chunk column, a fifth numeric list. list_len < 0, or
+ * list_len > 0 with a null list, is YT_ERR_INVALID_PLAN. The CPU oracle does
+ * not know this node. */
 
 /* STRING projections (GPU entries; plain scans: agg_count == 0 and
  * key_count == 0). A projection that is exactly YT_EX_COLUMN over a STRING
@@ -164,8 +198,18 @@ typedef struct YtExpr {
     double lit_dbl;       /* for YT_EX_LIT_DOUBLE */
     const struct YtExpr* a;
     const struct YtExpr* b;
-    const char* lit_str;  /* for YT_EX_LIT_STRING */
-    int64_t lit_len;
+    /* The last two words serve two node kinds that never coincide, under
+     * two names each (C11 / C++ anonymous unions): the struct keeps its 56
+     * bytes and every offset, so a caller built against the struct without
+     * `list` is laid out as before. */
+    union {
+        const char* lit_str;    /* for YT_EX_LIT_STRING */
+        const YtValue* list;    /* for YT_EX_IN: list_len values */
+    };
+    union {
+        int64_t lit_len;
+        int64_t list_len;
+    };
 } YtExpr;
 
 enum {
@@ -524,6 +568,12 @@ int32_t yt_gpu_debug_partition_tile_rows(int large);
  * summed over its predicates; 0 when it had none. */
 uint64_t yt_gpu_debug_last_strpred_entries(void);
 
+/* Diagnostic only: where the string IN lists of the calling thread's last
+ * query probed their slot tables. 0 = it had none with a bitmap, 1 = every
+ * table was staged in LDS, 2 = at least one was too large for that and was
+ * probed in global memory. */
+int32_t yt_gpu_debug_last_inlist_mode(void);
+
 /* Diagnostic only: blocks of the library's device/pinned buffer pool that
  * are taken and not yet given back, over all threads. A finished call holds
  * none, except what it handed out (a yt_gpu_versioned_scan_chunk handle until
@@ -701,6 +751,22 @@ int64_t yt_bitpack(const uint64_t* values, int64_t n, uint64_t max_value, uint64
  * escape. Needs no GPU. */
 int yt_strpred_eval(int op, int escape, const char* text, int64_t text_len,
                     const char* lit, int64_t lit_len);
+
+/* YT_EX_IN lookup tables, exposed for format tests: build the table of a
+ * list exactly as a query does and probe it on the CPU. Need no GPU.
+ * Numeric: list[0..n) are raw 64-bit patterns (int64, uint64 or boolean),
+ * has_null = the list also holds null; values[0..m) / nulls[0..m) (nulls
+ * may be NULL) are the operands; out[i] = 0 or 1. Returns YT_OK, or
+ * YT_ERR_UNSUPPORTED for a list over the length cap. */
+int yt_inlist_eval_i64(const uint64_t* list, int64_t n, int has_null,
+                       const uint64_t* values, const uint8_t* nulls, int64_t m,
+                       uint8_t* out);
+/* String: list entry i is list_bytes[list_ends[i-1] .. list_ends[i])
+ * (list_ends[-1] = 0), a null entry when list_nulls[i]; texts likewise. */
+int yt_inlist_eval_str(const char* list_bytes, const int64_t* list_ends,
+                       const uint8_t* list_nulls, int64_t n,
+                       const char* text_bytes, const int64_t* text_ends,
+                       const uint8_t* text_nulls, int64_t m, uint8_t* out);
 
 #ifdef __cplusplus
 } /* extern "C" */

@@ -46,6 +46,7 @@ EX_ADD, EX_SUB, EX_MUL, EX_DIV, EX_MOD = 10, 11, 12, 13, 14
 EX_EQ, EX_NE, EX_LT, EX_LE, EX_GT, EX_GE = 20, 21, 22, 23, 24, 25
 EX_AND, EX_OR, EX_NOT = 30, 31, 32
 EX_IS_PREFIX, EX_IS_SUBSTR, EX_LIKE = 40, 41, 42
+EX_IN = 43
 
 AGG_SUM = 0
 AGG_SUM1 = 1
@@ -99,10 +100,21 @@ class YtExpr(C.Structure):
     pass
 
 
+class _YtExprPtr(C.Union):
+    _fields_ = [("lit_str", C.c_void_p), ("list", C.POINTER(YtValue))]
+
+
+class _YtExprLen(C.Union):
+    _fields_ = [("lit_len", C.c_int64), ("list_len", C.c_int64)]
+
+
+# the header's two anonymous unions: lit_str / list and lit_len / list_len
+# share a word each, so the struct is 56 bytes with or without YT_EX_IN
+YtExpr._anonymous_ = ("ptr_", "len_")
 YtExpr._fields_ = [("op", C.c_int32), ("col", C.c_int32),
                    ("lit_i64", C.c_int64), ("lit_dbl", C.c_double),
                    ("a", C.POINTER(YtExpr)), ("b", C.POINTER(YtExpr)),
-                   ("lit_str", C.c_void_p), ("lit_len", C.c_int64)]
+                   ("ptr_", _YtExprPtr), ("len_", _YtExprLen)]
 
 
 class YtAgg(C.Structure):
@@ -247,6 +259,13 @@ def gpu_lib():
         _sig(lib, "yt_gpu_debug_pool_blocks_in_use", C.c_uint64, [])
         _sig(lib, "yt_strpred_eval", C.c_int,
              [C.c_int, C.c_int, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64])
+        _sig(lib, "yt_gpu_debug_last_inlist_mode", C.c_int32, [])
+        _sig(lib, "yt_inlist_eval_i64", C.c_int,
+             [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+              C.c_int64, C.c_void_p])
+        _sig(lib, "yt_inlist_eval_str", C.c_int,
+             [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64,
+              C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
         _sig(lib, "yt_gpu_query_partial", C.c_int,
              [C.POINTER(YtPlan), C.POINTER(YtChunk), C.POINTER(YtExecOptions),
               C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),

@@ -12,7 +12,7 @@ from ._abi import (
     YtExecOptions, YtStatistics, YtRowset, YtStateRow, YtEncodedColumn,
     VT_NULL, VT_INT64, VT_UINT64, VT_DOUBLE, VT_BOOLEAN, VT_STRING,
     EX_COLUMN, EX_LIT_I64, EX_LIT_NULL, EX_LIT_DOUBLE, EX_LIT_STRING,
-    EX_IS_PREFIX, EX_IS_SUBSTR, EX_LIKE,
+    EX_IS_PREFIX, EX_IS_SUBSTR, EX_LIKE, EX_IN,
     EX_ADD, EX_SUB, EX_MUL, EX_DIV, EX_MOD,
     EX_EQ, EX_NE, EX_LT, EX_LE, EX_GT, EX_GE, EX_AND, EX_OR, EX_NOT,
     AGG_SUM, AGG_SUM1, AGG_MIN, AGG_MAX, AGG_FIRST, AGG_AVG, YT_OK,
@@ -20,7 +20,7 @@ from ._abi import (
 
 __all__ = [
     "col", "lit", "null", "litf", "lit_str", "is_prefix", "is_substr", "like",
-    "strpred_eval", "Plan", "Join", "agg_sum", "agg_sum1",
+    "isin", "strpred_eval", "Plan", "Join", "agg_sum", "agg_sum1",
     "agg_first", "agg_avg", "agg_min", "agg_max",
     "encode_int64", "encode_double", "encode_bool", "encode_string", "encode_string_raw",
     "oracle_decode_strings", "encode_versioned_int64", "encode_versioned_double", "encode_versioned_string", "oracle_versioned_read", "gpu_versioned_read", "gpu_versioned_scan_chunk", "gpu_versioned_scan_table", "ScanChunk", "VersionedColumn",
@@ -71,6 +71,7 @@ class Expr:
     def and_(self, o): return self._bin(EX_AND, o)
     def or_(self, o): return self._bin(EX_OR, o)
     def not_(self): return Expr(EX_NOT, a=self)
+    def isin(self, values, unsigned=False): return isin(self, values, unsigned)
     __hash__ = None
 
 
@@ -139,6 +140,67 @@ def like(expr, pattern, escape=None):
     return Expr(EX_LIKE, lit_i64=esc, a=_coerce(expr), b=_coerce(pattern))
 
 
+_YTVALUE_DT = np.dtype([("id", "<u2"), ("type", "u1"), ("flags", "u1"),
+                        ("length", "<u4"), ("bits", "<u8")])
+assert _YTVALUE_DT.itemsize == C.sizeof(YtValue)
+
+
+def _in_list(values, unsigned):
+    """values -> (numpy YtValue array, keep-alive objects)"""
+    keep = []
+    if isinstance(values, np.ndarray):
+        if values.dtype not in (np.dtype(np.int64), np.dtype(np.uint64)):
+            raise TypeError("isin: numpy lists are int64 or uint64 arrays")
+        arr = np.zeros(len(values), dtype=_YTVALUE_DT)
+        arr["type"] = VT_UINT64 if values.dtype == np.uint64 else VT_INT64
+        arr["bits"] = np.ascontiguousarray(values).view(np.uint64)
+        return arr, keep
+    values = list(values)
+    arr = np.zeros(len(values), dtype=_YTVALUE_DT)
+    strs = [(i, _bytes(v)) for i, v in enumerate(values)
+            if isinstance(v, (bytes, bytearray, str))]
+    if strs:
+        # one buffer for all bytes; a value points into it
+        buf = C.create_string_buffer(b"".join(b for _, b in strs),
+                                     max(sum(len(b) for _, b in strs), 1))
+        keep.append(buf)
+        at = C.addressof(buf)
+        for i, b in strs:
+            arr[i] = (0, VT_STRING, 0, len(b), at)
+            at += len(b)
+    for i, v in enumerate(values):
+        if v is None:
+            arr[i] = (0, VT_NULL, 0, 0, 0)
+        elif isinstance(v, (bool, np.bool_)):
+            arr[i] = (0, VT_BOOLEAN, 0, 0, int(v))
+        elif isinstance(v, (int, np.integer)):
+            arr[i] = (0, VT_UINT64 if unsigned else VT_INT64, 0, 0,
+                      int(v) & ((1 << 64) - 1))
+        elif isinstance(v, float):
+            arr[i] = (0, VT_DOUBLE, 0, 0,
+                      int(np.float64(v).view(np.uint64)))
+        elif not isinstance(v, (bytes, bytearray, str)):
+            raise TypeError(v)
+    return arr, keep
+
+
+def isin(expr, values, unsigned=False):
+    """expr IN (values): a non-null boolean, true iff expr equals one of the
+    values; null matches None. values: a list of int / bool / bytes / None
+    (ints are uint64 values with unsigned=True), or a numpy int64 / uint64
+    array for long lists. A tuple of expressions as `expr` builds the tuple
+    form, which the library refuses."""
+    b = None
+    if isinstance(expr, (tuple, list)):
+        expr, b = _coerce(expr[0]), _coerce(expr[1])
+    e = Expr(EX_IN, a=_coerce(expr), b=b)
+    arr, keep = _in_list(values, unsigned)
+    e.c.list = C.cast(C.c_void_p(arr.ctypes.data), C.POINTER(YtValue))
+    e.c.list_len = len(arr)
+    e._list = (arr, keep)
+    return e
+
+
 def strpred_eval(op, text, literal, escape=None):
     """TEST ONLY: one string predicate on one non-null text through the host
     build of the GPU matchers (yt_strpred_eval). Returns 0/1, negative on
@@ -152,19 +214,21 @@ def _has_string_nodes(e):
     """does a YtExpr tree (ctypes) hold a node the oracle does not know?"""
     if e is None:
         return False
-    if e.c.op in (EX_LIT_STRING, EX_IS_PREFIX, EX_IS_SUBSTR, EX_LIKE):
+    if e.c.op in (EX_LIT_STRING, EX_IS_PREFIX, EX_IS_SUBSTR, EX_LIKE, EX_IN):
         return True
     return any(_has_string_nodes(k) for k in e._keep if isinstance(k, Expr))
 
 
 def _oracle_refuse_strings(plan):
     """The oracle's eval_expr would dereference the NULL children of an
-    unknown leaf: never hand it a plan with string literals / functions."""
+    unknown leaf: never hand it a plan with string literals / functions or
+    an IN list."""
     exprs = [plan.filter, plan.having] + list(plan.keys) + list(plan.projects)
     exprs += [arg for _, arg in plan.aggs]
     if any(_has_string_nodes(e) for e in exprs):
         raise NotImplementedError(
-            "the CPU oracle has no string literals or string predicates")
+            "the CPU oracle has no string literals or string predicates "
+            "and no IN lists")
 
 
 def agg_sum(e):

@@ -26,6 +26,7 @@ def build_gpu(force=False):
             for f in ("kernels.hip", "evaluator.cpp", "encoder.cpp")]
     hdrs = [os.path.join(HERE, "csrc", "common.h"),
             os.path.join(HERE, "csrc", "strpred.h"),
+            os.path.join(HERE, "csrc", "inlist.h"),
             os.path.join(REPO, "include", "ytql_gpu.h")]
     out = os.path.join(HERE, "libytql_gpu.so")
     if not force and _newer(out, srcs + hdrs):

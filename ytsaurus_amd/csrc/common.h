@@ -57,12 +57,18 @@ enum POp : int32_t {
      * and bits = (global DevSeg index << 32) | (entry id - 1): the entry that
      * dict_entry() resolves to the value's bytes (StrGatherRec.ref). */
     P_STR_REF = 51,
+    /* numeric YT_EX_IN, postfix: pops the operand, pushes a non-null
+     * boolean. bits = set index (low 8 bits) | kInNullRes = the list holds
+     * null (the answer for a null operand). The set is DevPlan in_tab /
+     * in_mask / in_empty (inlist.h inlist_probe_u64). */
+    P_IN_NUM = 52,
 };
 
 constexpr uint64_t kSpNullRes = 1ULL << 8;
 constexpr uint64_t kSpNullIsNull = 1ULL << 9;
 constexpr uint64_t kSpConst = 1ULL << 10;
 constexpr uint64_t kSpConstRes = 1ULL << 11;
+constexpr uint64_t kInNullRes = 1ULL << 8;
 
 struct PInst {
     int32_t op;
@@ -74,6 +80,7 @@ constexpr int kMaxProg = 48;
 constexpr int kMaxCols = 8;
 constexpr int kMaxAggs = 4;
 constexpr int kMaxStrPreds = 4;    /* string predicates with a bitmap per filter */
+constexpr int kMaxInSets = 4;      /* numeric IN lists per plan */
 
 /* The scalar words of the chunk setup (k_parse_segments, k_scan_nullflags,
  * the kernels' error word) in one block: one H2D copy of a host image sets
@@ -125,6 +132,12 @@ struct DevPlan {
     int32_t sp_count;
     const uint64_t* sp_bits[kMaxStrPreds];
     const int64_t* sp_base[kMaxStrPreds];
+    /* numeric IN sets (P_IN_NUM): open-addressing tables of the lists'
+     * distinct values, device pointers filled by the host (inlist.h); the
+     * program alone says how many are in use */
+    const uint64_t* in_tab[kMaxInSets];
+    uint64_t in_mask[kMaxInSets];
+    uint64_t in_empty[kMaxInSets];
 };
 
 /* Equi-join device context (one join item, UNIQUE foreign keys — see

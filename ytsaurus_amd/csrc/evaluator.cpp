@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "strpred.h"
+#include "inlist.h"
 #include "../../include/ytql_gpu.h"
 
 using namespace ytql;
@@ -143,6 +144,10 @@ hipError_t ytql_launch_strpred_entries(const DevSeg*, const SegEx*, int, int,
                                        const int64_t*, int64_t, int, int,
                                        const char*, int64_t, uint64_t*,
                                        hipStream_t);
+hipError_t ytql_launch_inlist_str_entries(const DevSeg*, const SegEx*, int, int,
+                                          const int64_t*, int64_t,
+                                          const InStrSlot*, uint64_t, const char*,
+                                          int, uint64_t*, hipStream_t);
 hipError_t ytql_launch_strgen_accum(const DevPlan*, const DevSeg*, const SegEx*,
                                     const int32_t*, const int32_t*, int, int64_t,
                                     const int64_t*, unsigned long long*,
@@ -401,7 +406,12 @@ extern "C" int yt_gpu_available(char* errbuf, size_t errlen)
 /* ------------------------------------------------------------------ */
 /* plan compilation: YtExpr tree → postfix DevPlan program              */
 
-static int compile_expr(const YtExpr* e, DevPlan* p, int* len, char* errbuf, size_t errlen)
+struct StrPreds;
+static int compile_in_num(const YtExpr* e, DevPlan* p, StrPreds* sp, int* len,
+                          char* errbuf, size_t errlen);
+
+static int compile_expr(const YtExpr* e, DevPlan* p, StrPreds* sp, int* len,
+                        char* errbuf, size_t errlen)
 {
     if (!e) { set_err(errbuf, errlen, "null expr"); return YT_ERR_INVALID_PLAN; }
     switch (e->op) {
@@ -410,15 +420,18 @@ static int compile_expr(const YtExpr* e, DevPlan* p, int* len, char* errbuf, siz
     case YT_EX_LIT_NULL:
     case YT_EX_LIT_DOUBLE:
         break;
+    case YT_EX_IN:
+        /* one operand and a literal list: the operand, then P_IN_NUM */
+        return compile_in_num(e, p, sp, len, errbuf, errlen);
     case YT_EX_NOT: {
-        int rc = compile_expr(e->a, p, len, errbuf, errlen);
+        int rc = compile_expr(e->a, p, sp, len, errbuf, errlen);
         if (rc) return rc;
         break;
     }
     default: {
-        int rc = compile_expr(e->a, p, len, errbuf, errlen);
+        int rc = compile_expr(e->a, p, sp, len, errbuf, errlen);
         if (rc) return rc;
-        rc = compile_expr(e->b, p, len, errbuf, errlen);
+        rc = compile_expr(e->b, p, sp, len, errbuf, errlen);
         if (rc) return rc;
         break;
     }
@@ -447,6 +460,7 @@ static uint8_t expr_static_type(const YtExpr* e, const uint8_t* col_types)
     case YT_EX_LIT_DOUBLE: return YT_VT_DOUBLE;
     case YT_EX_LIT_NULL: return YT_VT_NULL;
     case YT_EX_NOT: return YT_VT_BOOLEAN;
+    case YT_EX_IN: return YT_VT_BOOLEAN;
     default:
         if (e->op >= YT_EX_EQ) return YT_VT_BOOLEAN;   /* cmp / and / or */
         return expr_static_type(e->a, col_types);      /* arithmetic */
@@ -466,8 +480,19 @@ static bool expr_reads_string(const YtExpr* e, const uint8_t* col_types, int nco
     if (e->op == YT_EX_LIT_I64 || e->op == YT_EX_LIT_NULL ||
         e->op == YT_EX_LIT_DOUBLE || e->op == YT_EX_LIT_STRING)
         return false;
+    if (e->op == YT_EX_IN)          /* one operand; b is unused */
+        return expr_reads_string(e->a, col_types, ncols);
     return expr_reads_string(e->a, col_types, ncols) ||
            (e->op != YT_EX_NOT && expr_reads_string(e->b, col_types, ncols));
+}
+
+/* does an IN list hold a string value? (a numeric IN is no string node) */
+static bool in_list_has_string(const YtExpr* e)
+{
+    if (!e->list) return false;
+    for (int64_t i = 0; i < e->list_len; i++)
+        if (e->list[i].type == YT_VT_STRING) return true;
+    return false;
 }
 
 /* does the expression hold a string literal or a string function? Only a
@@ -481,6 +506,8 @@ static bool expr_has_strlit(const YtExpr* e)
     if (e->op == YT_EX_COLUMN || e->op == YT_EX_LIT_I64 ||
         e->op == YT_EX_LIT_NULL || e->op == YT_EX_LIT_DOUBLE)
         return false;
+    if (e->op == YT_EX_IN)
+        return in_list_has_string(e) || expr_has_strlit(e->a);
     return expr_has_strlit(e->a) ||
            (e->op != YT_EX_NOT && expr_has_strlit(e->b));
 }
@@ -493,26 +520,213 @@ static bool expr_has_strlit(const YtExpr* e)
 
 struct StrPredDesc {
     int op;                /* YT_EX_EQ..GE (column on the left), IS_PREFIX,
-                              IS_SUBSTR or LIKE */
+                              IS_SUBSTR, LIKE, or YT_EX_IN (the list is
+                              StrPreds::il of the same index) */
     int escape;            /* LIKE: 0..255, or -1 */
     int col;
     const char* lit;       /* the plan's bytes; alive for the whole call */
     int64_t lit_len;
 };
 
+/* a string IN list as the entry kernel reads it (inlist.h) */
+struct InStrList {
+    std::vector<char> bytes;
+    std::vector<InStrSlot> slots;
+    uint64_t mask = 0;
+};
+
+/* a numeric IN list: the distinct non-null values as raw 64-bit patterns,
+ * ascending; the device table is built from it (setup_string_preds) and
+ * heval searches it */
+struct InNumSet {
+    const YtExpr* e = nullptr;
+    std::vector<uint64_t> sorted;
+    bool has_null = false;
+    uint8_t type = 0;      /* YT_VT_* of the values; 0 = nulls only */
+};
+
+/* what a plan's filter (string predicates) and expressions (numeric IN
+ * sets) need on the device beside the program */
 struct StrPreds {
     int count = 0;                  /* leaves that need a bitmap */
     bool any = false;               /* any leaf, bitmap-less ones included */
+    int primary_ncols = 0;          /* columns below this are the chunk's own */
     StrPredDesc d[kMaxStrPreds];
+    InStrList il[kMaxStrPreds];     /* d[i].op == YT_EX_IN */
+    int in_count = 0;               /* numeric IN sets */
+    InNumSet in[kMaxInSets];
     PoolScope ps;                   /* pooled device buffers of this run */
     std::vector<int64_t> h_base[kMaxStrPreds];   /* upload sources */
+    std::vector<uint64_t> h_intab[kMaxInSets];
 };
 
 static thread_local uint64_t t_last_strpred_entries = 0;
+static thread_local int32_t t_last_inlist_mode = 0;
 
 extern "C" uint64_t yt_gpu_debug_last_strpred_entries(void)
 {
     return t_last_strpred_entries;
+}
+
+extern "C" int32_t yt_gpu_debug_last_inlist_mode(void)
+{
+    return t_last_inlist_mode;
+}
+
+/* the list of a YT_EX_IN node is well formed */
+static int in_list_shape(const YtExpr* e, char* errbuf, size_t errlen)
+{
+    if (e->list_len < 0 || (e->list_len > 0 && !e->list)) {
+        set_err(errbuf, errlen, "IN: negative list_len, or a list without values");
+        return YT_ERR_INVALID_PLAN;
+    }
+    if (e->b) {
+        set_err(errbuf, errlen, "IN over a tuple operand: not this round");
+        return YT_ERR_UNSUPPORTED;
+    }
+    return YT_OK;
+}
+
+static int in_list_too_long(char* errbuf, size_t errlen)
+{
+    if (errbuf && errlen)
+        snprintf(errbuf, errlen,
+                 "IN list longer than %lld distinct values: unsupported",
+                 (long long)kInListMax);
+    return YT_ERR_UNSUPPORTED;
+}
+
+/* sort and deduplicate a numeric list whose values have type vt (or are
+ * null); a boolean is its truth value */
+static int in_num_prepare(const YtExpr* e, uint8_t vt, InNumSet* s,
+                          char* errbuf, size_t errlen)
+{
+    s->e = e;
+    s->type = vt;
+    s->has_null = false;
+    s->sorted.clear();
+    s->sorted.reserve((size_t)e->list_len);
+    for (int64_t i = 0; i < e->list_len; i++) {
+        const YtValue& v = e->list[i];
+        if (v.type == YT_VT_NULL) { s->has_null = true; continue; }
+        if (v.type != vt) {
+            set_err(errbuf, errlen,
+                    "type mismatch: an IN list value has another type than "
+                    "the operand");
+            return YT_ERR_INVALID_PLAN;
+        }
+        s->sorted.push_back(vt == YT_VT_BOOLEAN ? (uint64_t)(v.data.bits != 0)
+                                                : v.data.bits);
+    }
+    std::sort(s->sorted.begin(), s->sorted.end());
+    s->sorted.erase(std::unique(s->sorted.begin(), s->sorted.end()),
+                    s->sorted.end());
+    if ((int64_t)s->sorted.size() > kInListMax)
+        return in_list_too_long(errbuf, errlen);
+    return YT_OK;
+}
+
+static int emit_inst(DevPlan* p, int op, int col, uint64_t bits,
+                     char* errbuf, size_t errlen);
+
+/* numeric YT_EX_IN: the operand's program, then one P_IN_NUM */
+static int compile_in_num(const YtExpr* e, DevPlan* p, StrPreds* sp, int* len,
+                          char* errbuf, size_t errlen)
+{
+    int rc = in_list_shape(e, errbuf, errlen);
+    if (rc) return rc;
+    if (!e->a) { set_err(errbuf, errlen, "null expr"); return YT_ERR_INVALID_PLAN; }
+    if (e->a->op == YT_EX_COLUMN && (e->a->col < 0 || e->a->col >= p->ncols)) {
+        set_err(errbuf, errlen, "column index out of range");
+        return YT_ERR_INVALID_PLAN;
+    }
+    const uint8_t vt = expr_static_type(e->a, p->col_types);
+    if (vt == YT_VT_DOUBLE) {
+        set_err(errbuf, errlen, "IN over a DOUBLE operand: not this round");
+        return YT_ERR_UNSUPPORTED;
+    }
+    if (vt == YT_VT_STRING) {
+        set_err(errbuf, errlen,
+                "IN: a string operand must be a plain string column of the "
+                "primary chunk, in the filter");
+        return YT_ERR_UNSUPPORTED;
+    }
+    if (vt != YT_VT_INT64 && vt != YT_VT_UINT64 && vt != YT_VT_BOOLEAN) {
+        set_err(errbuf, errlen,
+                "type mismatch: IN takes an int64, uint64 or boolean operand");
+        return YT_ERR_INVALID_PLAN;
+    }
+    if (!sp || sp->in_count >= kMaxInSets) {
+        set_err(errbuf, errlen,
+                "more than 4 numeric IN lists in one plan: not this round");
+        return YT_ERR_UNSUPPORTED;
+    }
+    /* the operand may hold an IN of its own: take the index first */
+    const int idx = sp->in_count++;
+    rc = in_num_prepare(e, vt, &sp->in[idx], errbuf, errlen);
+    if (rc) return rc;
+    rc = compile_expr(e->a, p, sp, len, errbuf, errlen);
+    if (rc) return rc;
+    rc = emit_inst(p, P_IN_NUM, 0,
+                   (uint64_t)idx | (sp->in[idx].has_null ? kInNullRes : 0),
+                   errbuf, errlen);
+    if (rc) return rc;
+    (*len)++;
+    return YT_OK;
+}
+
+extern "C" int yt_inlist_eval_i64(const uint64_t* list, int64_t n, int has_null,
+                                  const uint64_t* values, const uint8_t* nulls,
+                                  int64_t m, uint8_t* out)
+{
+    if (n < 0 || m < 0 || (n && !list) || (m && (!values || !out)))
+        return YT_ERR_INVALID_PLAN;
+    std::vector<uint64_t> sorted(list, list + n);
+    std::sort(sorted.begin(), sorted.end());
+    sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
+    if ((int64_t)sorted.size() > kInListMax) return YT_ERR_UNSUPPORTED;
+    std::vector<uint64_t> tab;
+    uint64_t mask = 0, empty = 0;
+    inlist_build_u64(sorted, &tab, &mask, &empty);
+    for (int64_t i = 0; i < m; i++)
+        out[i] = (nulls && nulls[i])
+            ? (uint8_t)(has_null != 0)
+            : (uint8_t)inlist_probe_u64(tab.data(), mask, empty, values[i]);
+    return YT_OK;
+}
+
+extern "C" int yt_inlist_eval_str(const char* list_bytes, const int64_t* list_ends,
+                                  const uint8_t* list_nulls, int64_t n,
+                                  const char* text_bytes, const int64_t* text_ends,
+                                  const uint8_t* text_nulls, int64_t m,
+                                  uint8_t* out)
+{
+    if (n < 0 || m < 0 || (n && !list_ends) || (m && (!text_ends || !out)))
+        return YT_ERR_INVALID_PLAN;
+    std::vector<const char*> ptr;
+    std::vector<uint32_t> len;
+    bool has_null = false;
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t b = i ? list_ends[i - 1] : 0;
+        if (list_nulls && list_nulls[i]) { has_null = true; continue; }
+        ptr.push_back(list_bytes + b);
+        len.push_back((uint32_t)(list_ends[i] - b));
+    }
+    InStrList il;
+    const int64_t distinct = inlist_build_str(ptr.data(), len.data(),
+                                              (int64_t)ptr.size(), &il.bytes,
+                                              &il.slots, &il.mask);
+    if (distinct < 0 || distinct > kInListMax) return YT_ERR_UNSUPPORTED;
+    for (int64_t i = 0; i < m; i++) {
+        const int64_t b = i ? text_ends[i - 1] : 0;
+        const uint32_t tn = (uint32_t)(text_ends[i] - b);
+        out[i] = (text_nulls && text_nulls[i])
+            ? (uint8_t)has_null
+            : (uint8_t)inlist_probe_str(il.slots.data(), il.mask, il.bytes.data(),
+                                        inlist_str_hash(text_bytes + b, tn),
+                                        text_bytes + b, tn);
+    }
+    return YT_OK;
 }
 
 extern "C" int yt_strpred_eval(int op, int escape, const char* text,
@@ -555,6 +769,63 @@ static int compile_str_leaf(const YtExpr* e, DevPlan* p, StrPreds* sp,
     memset(&d, 0, sizeof(d));
     d.escape = -1;
     const YtExpr* lit = nullptr;
+    if (e->op == YT_EX_IN) {
+        const bool str_operand = is_string_col(e->a, p) ||
+                                 (e->a && e->a->op == YT_EX_LIT_STRING);
+        if (!str_operand) return YT_OK;       /* numeric form, or a mismatch */
+        int rc = in_list_shape(e, errbuf, errlen);
+        if (rc) return rc;
+        if (e->a->op != YT_EX_COLUMN || e->a->col >= sp->primary_ncols) {
+            set_err(errbuf, errlen,
+                    "IN: a string operand must be a plain string column of "
+                    "the primary chunk, in the filter");
+            return YT_ERR_UNSUPPORTED;
+        }
+        std::vector<const char*> ptr;
+        std::vector<uint32_t> len;
+        bool has_null = false;
+        for (int64_t i = 0; i < e->list_len; i++) {
+            const YtValue& v = e->list[i];
+            if (v.type == YT_VT_NULL) { has_null = true; continue; }
+            if (v.type != YT_VT_STRING) {
+                set_err(errbuf, errlen,
+                        "type mismatch: an IN list value has another type "
+                        "than the operand");
+                return YT_ERR_INVALID_PLAN;
+            }
+            if (v.length > 0 && !v.data.str) {
+                set_err(errbuf, errlen, "string literal without bytes");
+                return YT_ERR_INVALID_PLAN;
+            }
+            ptr.push_back(v.data.str);
+            len.push_back(v.length);
+        }
+        sp->any = true;
+        *matched = 1;
+        if (ptr.empty()) {
+            /* no value to match: false for every text, the list's null flag
+             * for a null text — constants, no bitmap */
+            return emit_inst(p, P_STR_PRED, e->a->col,
+                             kSpConst | (has_null ? kSpNullRes : 0),
+                             errbuf, errlen);
+        }
+        if (sp->count >= kMaxStrPreds) {
+            set_err(errbuf, errlen,
+                    "more than 4 string predicates in one filter: not this round");
+            return YT_ERR_UNSUPPORTED;
+        }
+        InStrList& il = sp->il[sp->count];
+        const int64_t distinct = inlist_build_str(ptr.data(), len.data(),
+                                                  (int64_t)ptr.size(), &il.bytes,
+                                                  &il.slots, &il.mask);
+        if (distinct < 0 || distinct > kInListMax)
+            return in_list_too_long(errbuf, errlen);
+        d.op = YT_EX_IN;
+        d.col = e->a->col;
+        const uint64_t bits = (uint64_t)sp->count | (has_null ? kSpNullRes : 0);
+        sp->d[sp->count++] = d;
+        return emit_inst(p, P_STR_PRED, d.col, bits, errbuf, errlen);
+    }
     if (e->op >= YT_EX_EQ && e->op <= YT_EX_GE) {
         int op = e->op;
         const YtExpr* colx = nullptr;
@@ -658,8 +929,6 @@ static int compile_str_leaf(const YtExpr* e, DevPlan* p, StrPreds* sp,
     return emit_inst(p, P_STR_PRED, d.col, bits, errbuf, errlen);
 }
 
-static int compile_expr(const YtExpr* e, DevPlan* p, int* len, char* errbuf, size_t errlen);
-
 /* the filter: AND/OR/NOT over string-predicate leaves and ordinary
  * subexpressions; sp == nullptr refuses every string predicate */
 static int compile_filter(const YtExpr* e, DevPlan* p, StrPreds* sp,
@@ -694,7 +963,7 @@ static int compile_filter(const YtExpr* e, DevPlan* p, StrPreds* sp,
         return YT_ERR_UNSUPPORTED;
     }
     int len = 0;
-    return compile_expr(e, p, &len, errbuf, errlen);
+    return compile_expr(e, p, sp, &len, errbuf, errlen);
 }
 
 static int build_devplan(const YtPlan* plan, const YtChunk* chunk, DevPlan* p,
@@ -702,6 +971,7 @@ static int build_devplan(const YtPlan* plan, const YtChunk* chunk, DevPlan* p,
 {
     memset(p, 0, sizeof(*p));
     p->ncols = chunk->column_count;
+    if (sp) sp->primary_ncols = chunk->column_count;
     for (const YtJoin* J = plan->join; J; J = J->next)
         p->ncols += J->foreign_value_count;
     if (p->ncols > kMaxCols) { set_err(errbuf, errlen, "too many columns"); return YT_ERR_UNSUPPORTED; }
@@ -799,7 +1069,7 @@ static int build_devplan(const YtPlan* plan, const YtChunk* chunk, DevPlan* p,
     }
     if (plan->key_count == 1) {
         p->key_off = p->prog_len;
-        rc = compile_expr(plan->keys[0], p, &p->key_len, errbuf, errlen);
+        rc = compile_expr(plan->keys[0], p, sp, &p->key_len, errbuf, errlen);
         if (rc) return rc;
         p->key_len = p->prog_len - p->key_off;
     }
@@ -841,7 +1111,7 @@ static int build_devplan(const YtPlan* plan, const YtChunk* chunk, DevPlan* p,
         }
         if (plan->aggs[a]->func != YT_AGG_SUM1) {
             p->agg_off[a] = p->prog_len;
-            rc = compile_expr(plan->aggs[a]->arg, p, &p->agg_len[a], errbuf, errlen);
+            rc = compile_expr(plan->aggs[a]->arg, p, sp, &p->agg_len[a], errbuf, errlen);
             if (rc) return rc;
             p->agg_len[a] = p->prog_len - p->agg_off[a];
         }
@@ -888,7 +1158,7 @@ static int build_devplan(const YtPlan* plan, const YtChunk* chunk, DevPlan* p,
                         "string column)");
                 return YT_ERR_UNSUPPORTED;
             }
-            rc = compile_expr(plan->projects[pj], p, &p->proj_len[pj], errbuf, errlen);
+            rc = compile_expr(plan->projects[pj], p, sp, &p->proj_len[pj], errbuf, errlen);
             if (rc) return rc;
             p->proj_len[pj] = p->prog_len - p->proj_off[pj];
         }
@@ -1024,9 +1294,84 @@ static void analyze_fast(const YtPlan* plan, const YtChunk* chunk, FastShape* fs
 
 struct HVal { uint8_t type; uint64_t bits; };
 
+static int heval(const YtExpr* e, const HVal* row, int nrow, HVal* out);
+
+/* The numeric IN lists of the expression heval is running (HAVING), sorted
+ * by hin_prepare on the calling thread; a node that is not among them is
+ * compared value by value. */
+static thread_local const std::vector<InNumSet>* t_hin = nullptr;
+
+static int hin_collect(const YtExpr* e, std::vector<InNumSet>* sets,
+                       char* errbuf, size_t errlen)
+{
+    if (!e) return YT_OK;
+    if (e->op == YT_EX_IN) {
+        int rc = in_list_shape(e, errbuf, errlen);
+        if (rc) return rc;
+        uint8_t vt = 0;
+        for (int64_t i = 0; i < e->list_len && !vt; i++)
+            if (e->list[i].type != YT_VT_NULL) vt = e->list[i].type;
+        if (vt == YT_VT_DOUBLE) {
+            set_err(errbuf, errlen, "IN over a DOUBLE operand: not this round");
+            return YT_ERR_UNSUPPORTED;
+        }
+        if (vt && vt != YT_VT_INT64 && vt != YT_VT_UINT64 && vt != YT_VT_BOOLEAN) {
+            set_err(errbuf, errlen,
+                    "type mismatch: IN takes an int64, uint64 or boolean operand");
+            return YT_ERR_INVALID_PLAN;
+        }
+        sets->emplace_back();
+        rc = in_num_prepare(e, vt, &sets->back(), errbuf, errlen);
+        if (rc) return rc;
+        return hin_collect(e->a, sets, errbuf, errlen);
+    }
+    int rc = hin_collect(e->a, sets, errbuf, errlen);
+    if (rc) return rc;
+    return hin_collect(e->b, sets, errbuf, errlen);
+}
+
+/* YT_EX_IN on the host: the operand equals one of the values; null matches
+ * null; the result is never null */
+static int heval_in(const YtExpr* e, const HVal* row, int nrow, HVal* out)
+{
+    if (!e->a || e->b || e->list_len < 0 || (e->list_len > 0 && !e->list))
+        return YT_ERR_INVALID_PLAN;
+    HVal a;
+    int rc = heval(e->a, row, nrow, &a);
+    if (rc) return rc;
+    if (a.type == YT_VT_DOUBLE || a.type == YT_VT_STRING) return YT_ERR_UNSUPPORTED;
+    const uint64_t abits = a.type == YT_VT_BOOLEAN ? (uint64_t)(a.bits != 0) : a.bits;
+    out->type = YT_VT_BOOLEAN;
+    out->bits = 0;
+    if (t_hin) {
+        for (const InNumSet& s : *t_hin) {
+            if (s.e != e) continue;
+            if (a.type == YT_VT_NULL) { out->bits = s.has_null; return YT_OK; }
+            if (s.type && s.type != a.type) return YT_ERR_INVALID_PLAN;
+            out->bits = std::binary_search(s.sorted.begin(), s.sorted.end(), abits);
+            return YT_OK;
+        }
+    }
+    for (int64_t i = 0; i < e->list_len; i++) {
+        const YtValue& v = e->list[i];
+        if (v.type == YT_VT_NULL) {
+            if (a.type == YT_VT_NULL) out->bits = 1;
+            continue;
+        }
+        if (a.type == YT_VT_NULL) continue;
+        if (v.type != a.type) return YT_ERR_INVALID_PLAN;
+        const uint64_t vb = v.type == YT_VT_BOOLEAN ? (uint64_t)(v.data.bits != 0)
+                                                    : v.data.bits;
+        if (vb == abits) out->bits = 1;
+    }
+    return YT_OK;
+}
+
 static int heval(const YtExpr* e, const HVal* row, int nrow, HVal* out)
 {
     switch (e->op) {
+    case YT_EX_IN:
+        return heval_in(e, row, nrow, out);
     case YT_EX_COLUMN:
         if (e->col < 0 || e->col >= nrow) return YT_ERR_INVALID_PLAN;
         *out = row[e->col];
@@ -1315,7 +1660,18 @@ static int setup_string_preds(StrPreds* sp, DeviceRun* R, DevPlan* dp,
     const bool timing = getenv("YTQL_TIMING") != nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     t_last_strpred_entries = 0;
+    t_last_inlist_mode = 0;
     dp->sp_count = sp->count;
+    /* numeric IN sets: one open-addressing table each (inlist.h) */
+    for (int i = 0; i < sp->in_count && R->nsegs != 0; i++) {
+        std::vector<uint64_t>& tab = sp->h_intab[i];
+        inlist_build_u64(sp->in[i].sorted, &tab, &dp->in_mask[i], &dp->in_empty[i]);
+        uint64_t* d_tab = nullptr;
+        HIP_CHECK(sp->ps.dev(&d_tab, sizeof(uint64_t) * tab.size()));
+        HIP_CHECK(hipMemcpyAsync(d_tab, tab.data(), sizeof(uint64_t) * tab.size(),
+                                 hipMemcpyHostToDevice, R->stream));
+        dp->in_tab[i] = d_tab;
+    }
     if (sp->count == 0 || R->nsegs == 0) return YT_OK;
     if (timing) {
         HIP_CHECK(ps.event(&e0));
@@ -1348,9 +1704,35 @@ static int setup_string_preds(StrPreds* sp, DeviceRun* R, DevPlan* dp,
         char* d_lit = nullptr;
         HIP_CHECK(sp->ps.dev(&d_base, sizeof(int64_t) * (cnt + 1)));
         HIP_CHECK(sp->ps.dev(&d_bits, sizeof(uint64_t) * (words ? words : 1)));
-        HIP_CHECK(sp->ps.dev(&d_lit, (size_t)(d.lit_len ? d.lit_len : 1)));
         HIP_CHECK(hipMemcpyAsync(d_base, base.data(), sizeof(int64_t) * (cnt + 1),
                                  hipMemcpyHostToDevice, R->stream));
+        if (d.op == YT_EX_IN) {
+            /* the list's slot table and bytes, then the IN entry kernel */
+            const InStrList& il = sp->il[i];
+            InStrSlot* d_slots = nullptr;
+            char* d_bytes = nullptr;
+            const size_t nb = il.bytes.size();
+            HIP_CHECK(sp->ps.dev(&d_slots, sizeof(InStrSlot) * il.slots.size()));
+            HIP_CHECK(sp->ps.dev(&d_bytes, nb ? nb : 1));
+            HIP_CHECK(hipMemcpyAsync(d_slots, il.slots.data(),
+                                     sizeof(InStrSlot) * il.slots.size(),
+                                     hipMemcpyHostToDevice, R->stream));
+            if (nb)
+                HIP_CHECK(hipMemcpyAsync(d_bytes, il.bytes.data(), nb,
+                                         hipMemcpyHostToDevice, R->stream));
+            const int use_lds = il.slots.size() <= kInStrLdsSlots;
+            if (words) {
+                HIP_CHECK(ytql_launch_inlist_str_entries(
+                    R->d_segs, R->d_segex, off, cnt, d_base, words, d_slots,
+                    il.mask, d_bytes, use_lds, d_bits, R->stream));
+                if (!use_lds) t_last_inlist_mode = 2;
+                else if (t_last_inlist_mode == 0) t_last_inlist_mode = 1;
+            }
+            dp->sp_bits[i] = d_bits;
+            dp->sp_base[i] = d_base;
+            continue;
+        }
+        HIP_CHECK(sp->ps.dev(&d_lit, (size_t)(d.lit_len ? d.lit_len : 1)));
         if (d.lit_len)
             HIP_CHECK(hipMemcpyAsync(d_lit, d.lit, (size_t)d.lit_len,
                                      hipMemcpyHostToDevice, R->stream));
@@ -2526,6 +2908,14 @@ static int finish_output(const YtPlan* plan, YtRowset* out,
         int ncols = out->column_count;
         uint64_t mask = 0;
         hexpr_cols(plan->having, &mask);
+        /* IN lists: sorted once, binary-searched per group row */
+        std::vector<InNumSet> hin;
+        int hrc = hin_collect(plan->having, &hin, errbuf, errlen);
+        if (hrc) return hrc;
+        struct HinScope {
+            HinScope(const std::vector<InNumSet>* s) { t_hin = s; }
+            ~HinScope() { t_hin = nullptr; }
+        } hin_scope(&hin);
         int64_t w = 0;
         HVal hrow[32];
         for (int64_t r = 0; r < out->row_count; r++) {
@@ -4462,6 +4852,7 @@ extern "C" int yt_gpu_query_execute(
     }
     output->totals_row = 0;
     t_last_strpred_entries = 0;
+    t_last_inlist_mode = 0;
     if (plan->having && expr_has_strlit(plan->having)) {
         set_err(errbuf, errlen, "HAVING over string values: not this round");
         return YT_ERR_UNSUPPORTED;
@@ -4753,6 +5144,7 @@ static int query_partial_impl(
 
     double tw0 = now_ms();
     t_last_strpred_entries = 0;
+    t_last_inlist_mode = 0;
     DevPlan dp;
     StrPreds SP;
     rc = build_devplan(plan, chunk, &dp, &SP, errbuf, errlen);
@@ -4950,6 +5342,7 @@ extern "C" int yt_gpu_query_partial_str(
     if (!options) options = &defopt;
     if (stats) memset(stats, 0, sizeof(*stats));
     t_last_strpred_entries = 0;
+    t_last_inlist_mode = 0;
     StrPartialOut po;
     po.partition_count = partition_count;
     po.states_device = (YtStateRow*)states_device;

@@ -25,6 +25,7 @@
 #include <atomic>
 #include "common.h"
 #include "strpred.h"
+#include "inlist.h"
 #include "../../include/ytql_gpu.h"
 
 namespace ytql {
@@ -821,6 +822,23 @@ __device__ __noinline__ DVal str_ref_row(const DevPlan& p, const ColCtx& c, cons
     return v;
 }
 
+/* P_IN_NUM: is the operand in the numeric IN set (common.h)? A mix64 probe
+ * loop over the set's open-addressing table, like join_resolve's; a null
+ * operand answers with the list's null flag. The result is never null. Out
+ * of line for the reason given at str_pred_row. */
+__device__ __noinline__ void in_num_row(const DevPlan& p, const PInst& in, DVal& v)
+{
+    if (v.null_) {
+        v.bits = (in.bits & kInNullRes) != 0;
+    } else {
+        const int si = (int)(in.bits & 0xFF);
+        v.bits = (uint64_t)inlist_probe_u64(p.in_tab[si], p.in_mask[si],
+                                            p.in_empty[si], v.bits);
+    }
+    v.type = YT_VT_BOOLEAN;
+    v.null_ = 0;
+}
+
 __device__ DVal eval_prog(const DevPlan& p, ColCtx& c, int off, int len)
 {
     DVal stk[12];
@@ -857,6 +875,9 @@ __device__ DVal eval_prog(const DevPlan& p, ColCtx& c, int off, int len)
             break;
         case P_STR_REF:
             stk[sp++] = str_ref_row(p, c, in);
+            break;
+        case P_IN_NUM:
+            in_num_row(p, in, stk[sp - 1]);
             break;
         default: {
             DVal b = stk[--sp];
@@ -3264,6 +3285,56 @@ k_strpred_entries(const DevSeg* segs, const SegEx* segex, int seg_off, int nsegs
     }
 }
 
+/* String IN entry pass (YT_EX_IN over a STRING column): the shape of
+ * k_strpred_entries — one wave64 per 64-bit answer word, a lane per entry,
+ * __ballot assembles the word, lane 0 stores it; no memset, no atomics —
+ * with the predicate "the entry's bytes are in the list". Each lane hashes
+ * its entry (inlist.h inlist_str_hash) and probes the list's slot table; a
+ * hash hit is confirmed on length and bytes. kLds: the table has at most
+ * kInStrLdsSlots slots and the workgroup copies it into LDS first (16-byte
+ * slots, one ds_read_b128 per probe step); otherwise the probes read global
+ * memory. The list's bytes stay in global memory either way. */
+template <bool kLds>
+__global__ void __launch_bounds__(256)
+k_inlist_str_entries(const DevSeg* segs, const SegEx* segex, int seg_off, int nsegs,
+                     const int64_t* pred_base, const InStrSlot* slots,
+                     uint64_t mask, const char* list_bytes, uint64_t* bits)
+{
+    __shared__ InStrSlot lds[kLds ? kInStrLdsSlots : 1];
+    const InStrSlot* tab = slots;
+    if (kLds) {
+        for (uint32_t i = threadIdx.x; i <= (uint32_t)mask && i < kInStrLdsSlots;
+             i += 256)
+            lds[i] = slots[i];
+        __syncthreads();
+        tab = lds;
+    }
+    const int lane = threadIdx.x & 63;
+    const int64_t nwords = pred_base[nsegs];
+    const int64_t wstride = (int64_t)gridDim.x * 4;
+    for (int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); w < nwords;
+         w += wstride) {
+        int lo = 0, hi = nsegs;
+        while (lo + 1 < hi) {
+            int mid = (lo + hi) / 2;
+            if (pred_base[mid] <= w) lo = mid;
+            else hi = mid;
+        }
+        const DevSeg& s = segs[seg_off + lo];
+        const SegEx& e = segex[seg_off + lo];
+        const int64_t j = (w - pred_base[lo]) * 64 + lane;
+        int res = 0;
+        if (j < (int64_t)e.dict_size) {
+            uint32_t len;
+            const char* t = dict_entry(s, e, j, &len);
+            res = inlist_probe_str(tab, mask, list_bytes,
+                                   inlist_str_hash(t, len), t, len);
+        }
+        const unsigned long long word = __ballot(res);
+        if (lane == 0) bits[w] = word;
+    }
+}
+
 /* ------------------------------------------------------------------ */
 /* scan + project with STRING projections: stable device compaction of  */
 /* one window and the byte gather (common.h ProjTot, StrGatherRec).     */
@@ -4717,6 +4788,29 @@ hipError_t ytql_launch_strpred_entries(const DevSeg* segs, const SegEx* segex,
     hipLaunchKernelGGL(k_strpred_entries, dim3(grid), dim3(256), 0, st,
                        segs, segex, seg_off, nsegs, pred_base, op, escape,
                        lit, lit_len, bits);
+    return hipGetLastError();
+}
+
+/* use_lds != 0 needs mask + 1 <= kInStrLdsSlots */
+hipError_t ytql_launch_inlist_str_entries(const DevSeg* segs, const SegEx* segex,
+                                          int seg_off, int nsegs,
+                                          const int64_t* pred_base,
+                                          int64_t nwords, const InStrSlot* slots,
+                                          uint64_t mask, const char* list_bytes,
+                                          int use_lds, uint64_t* bits,
+                                          hipStream_t st)
+{
+    int64_t want = (nwords + 3) / 4;      /* one wave64 per word */
+    int grid = (int)(want > 4096 ? 4096 : (want > 0 ? want : 1));
+    if (use_lds && mask + 1 > kInStrLdsSlots) return hipErrorInvalidValue;
+    if (use_lds)
+        hipLaunchKernelGGL(k_inlist_str_entries<true>, dim3(grid), dim3(256), 0, st,
+                           segs, segex, seg_off, nsegs, pred_base, slots, mask,
+                           list_bytes, bits);
+    else
+        hipLaunchKernelGGL(k_inlist_str_entries<false>, dim3(grid), dim3(256), 0, st,
+                           segs, segex, seg_off, nsegs, pred_base, slots, mask,
+                           list_bytes, bits);
     return hipGetLastError();
 }
 
