@@ -375,26 +375,28 @@ struct StrGroupParams {
     int32_t tiles_per_seg;
     int32_t ntiles;
     int32_t has_val_nulls;
-    int32_t xcd_affine;           /* keep each segment's accumulators in one
-                                     XCD's L2 (blockIdx%8 = XCD round-robin) */
     int64_t row_count;
 };
 
-/* merge-table slot: rep = (seg+1)<<32 | id (1-based), 0 = empty.
- * The representative's hash is NOT stored: readers recompute it from the
- * precomputed per-entry hash array via (seg, id), which avoids any
- * publication ordering between the claim and a hash field. */
-/* 64-byte slot, one cache line: rep claims the slot (CAS); the claimer
+/* merge-table slot of every string-key merge. The protocol below is written
+ * once, in kernels.hip strslot_find_or_claim; what differs per merge is the
+ * Key it is given. rep names the slot's owner, 0 = empty:
+ *   dictionary entry (k_strgrp_merge, k_strgen_merge)  (seg+1)<<32 | 1-based id
+ *   exchanged state  (k_strst_merge)                   state index + 1
+ * The owner's hash is NOT stored: readers recompute it from the
+ * precomputed per-key hash array via rep, which avoids any publication
+ * ordering between the claim and a hash field.
+ * 64-byte slot, one cache line: rep claims the slot (CAS); the claimer
  * then publishes the key identity in-slot with RELAXED agent stores —
  * ident = hash48|len16, pfx = the key's first 16 bytes. Readers verify
  * with relaxed loads; a stale (zero / partially visible) identity only
  * demotes the probe to the exact owner-array compare, never a wrong
  * accept: ident mismatch is exact (FNV48+len of equal strings always
  * match), ident match with len <= 16 is decided by pfx (the FULL bytes),
- * len > 16 falls back to the byte compare against the owner's dictionary
- * entry. */
+ * len > 16 falls back to the byte compare against the owner's bytes
+ * (Key::equals_owner). */
 struct StrSlot {
-    unsigned long long rep;       /* (seg+1)<<32 | id; 0 = empty */
+    unsigned long long rep;       /* names the owner (above); 0 = empty */
     uint64_t ident;               /* hash48<<16 | len; 0 = unpublished */
     uint64_t pfx[2];              /* first 16 key bytes, zero-padded */
     uint64_t sum_bits;

@@ -24,164 +24,10 @@
 #include "common.h"
 #include "strpred.h"
 #include "inlist.h"
+#include "launch.h"
 #include "../../include/ytql_gpu.h"
 
 using namespace ytql;
-
-/* launch wrappers from kernels.hip */
-extern "C" {
-hipError_t ytql_launch_parse_segments(const DevSeg*, int, SegEx*, unsigned*, unsigned*, unsigned long long*, unsigned long long*, hipStream_t);
-hipError_t ytql_launch_scan_nullflags(const DevSeg*, const SegEx*, int, unsigned*, hipStream_t);
-hipError_t ytql_launch_scan_zzrange(const DevSeg*, const SegEx*, int, int, int,
-                                    unsigned long long*, hipStream_t);
-hipError_t ytql_launch_scan_partition(const PartParams*, const DevSeg*, const SegEx*,
-                                      const FastCol*, TableHdr*, unsigned long long*,
-                                      void*, unsigned long long*, uint64_t*,
-                                      int, hipStream_t);
-hipError_t ytql_launch_bucket_agg(const void*, const unsigned long long*, int64_t,
-                                  const uint64_t*, const unsigned long long*, int64_t,
-                                  OutGroup*, unsigned long long*, int64_t, int,
-                                  TableHdr*, int, int, int, int,
-                                  uint64_t, uint64_t, int, hipStream_t);
-hipError_t ytql_launch_bucket_agg_direct(const void*, const unsigned long long*, int64_t,
-                                         const uint64_t*, const unsigned long long*, int64_t,
-                                         OutGroup*, unsigned long long*, int64_t, int,
-                                         TableHdr*, int, int, int, int,
-                                         uint64_t, uint64_t, int, int, hipStream_t);
-hipError_t ytql_launch_topk_hist(const DevPlan*, const DevSeg*, const SegEx*,
-                                 const int32_t*, const int32_t*, int64_t,
-                                 const JoinDev*, const JoinDev*,
-                                 const TopkPass*, unsigned long long*,
-                                 unsigned long long*, unsigned*, hipStream_t);
-hipError_t ytql_launch_topk_gather(const DevPlan*, const DevSeg*, const SegEx*,
-                                   const int32_t*, const int32_t*, int64_t,
-                                   const JoinDev*, const JoinDev*,
-                                   const TopkGather*,
-                                   int64_t*, unsigned long long*,
-                                   int64_t*, unsigned long long*,
-                                   int64_t*, unsigned long long*,
-                                   unsigned*, hipStream_t);
-hipError_t ytql_launch_topk_materialize(const DevPlan*, const DevSeg*, const SegEx*,
-                                        const int32_t*, const int32_t*,
-                                        const JoinDev*, const JoinDev*,
-                                        const int64_t*, int64_t, DevOutVal*,
-                                        unsigned*, hipStream_t);
-hipError_t ytql_launch_topk_hist_fast(const DevSeg*, const SegEx*, int, int,
-                                      int64_t, int, int, const TopkPass*,
-                                      unsigned long long*, unsigned long long*,
-                                      hipStream_t);
-hipError_t ytql_launch_topk_gather_fast(const DevSeg*, const SegEx*, int, int,
-                                        int64_t, int, int, const TopkGather*,
-                                        int64_t*, unsigned long long*,
-                                        int64_t*, unsigned long long*,
-                                        int64_t*, unsigned long long*,
-                                        hipStream_t);
-hipError_t ytql_launch_versioned_read(const VSegDev*, int, int64_t, uint64_t,
-                                      uint64_t*, uint8_t*, uint8_t*, uint8_t*,
-                                      hipStream_t);
-hipError_t ytql_launch_vis_count(const uint8_t*, int64_t,
-                                 unsigned long long*, int, hipStream_t);
-hipError_t ytql_launch_unvcol_to_arrays(const DevSeg*, const SegEx*, int, int,
-                                        int64_t, uint64_t*, uint8_t*,
-                                        unsigned*, hipStream_t);
-hipError_t ytql_launch_vis_scatter(const uint8_t*, const uint8_t*,
-                                   const uint64_t*, int64_t,
-                                   const unsigned long long*, uint64_t,
-                                   const int64_t*, char*, int, int, hipStream_t);
-hipError_t ytql_launch_join_build(const JoinDev*, int64_t, uint64_t*,
-                                  long long*, unsigned long long*, unsigned*,
-                                  hipStream_t);
-hipError_t ytql_launch_join_chain(const JoinDev*, int64_t, unsigned*,
-                                   hipStream_t);
-hipError_t ytql_launch_scan_project(const DevPlan*, const DevSeg*, const SegEx*,
-                                    const int32_t*, const int32_t*, int64_t,
-                                    int64_t, const JoinDev*, const JoinDev*,
-                                    DevOutVal*, uint8_t*, unsigned*, hipStream_t);
-hipError_t ytql_launch_proj_offsets(const DevSeg*, const SegEx*, DevOutVal*,
-                                    const uint8_t*, int64_t, int, unsigned,
-                                    ProjTot*, ProjTot*, hipStream_t);
-hipError_t ytql_launch_proj_scatter(const DevOutVal*, const uint8_t*, int64_t,
-                                    int, unsigned, int, const ProjTot*,
-                                    DevOutVal*, StrGatherRec*, hipStream_t);
-hipError_t ytql_launch_str_reclen(const DevSeg*, const SegEx*, StrGatherRec*,
-                                  int64_t, hipStream_t);
-hipError_t ytql_launch_str_gather(const DevSeg*, const SegEx*,
-                                  const StrGatherRec*, int64_t, char*, uint64_t,
-                                  hipStream_t);
-hipError_t ytql_launch_scan_generic(const DevPlan*, const DevSeg*, const SegEx*,
-                                    const int32_t*, const int32_t*, int64_t,
-                                    const JoinDev*, const JoinDev*,
-                                    TableHdr*, unsigned long long*, unsigned*, hipStream_t);
-hipError_t ytql_launch_scan_fast(const FastParams*, const DevSeg*, const SegEx*,
-                                 const FastCol*, TableHdr*, unsigned long long*,
-                                 unsigned long long*, size_t, int, hipStream_t);
-hipError_t ytql_launch_compact(TableHdr*, TableHdr*, const unsigned long long*, int,
-                               OutGroup*, unsigned long long*, uint64_t, hipStream_t);
-hipError_t ytql_launch_part_count(const OutGroup*, int64_t, int, int,
-                                  unsigned long long*, hipStream_t);
-hipError_t ytql_launch_part_scatter(const OutGroup*, int64_t, int, int, int,
-                                    int, unsigned long long*, YtStateRow*,
-                                    hipStream_t);
-hipError_t ytql_launch_merge_states(const YtStateRow*, int64_t, int, int,
-                                    int, TableHdr*, unsigned long long*,
-                                    hipStream_t);
-hipError_t ytql_launch_strgrp_accum(const StrGroupParams*, const DevSeg*, const SegEx*,
-                                    const int64_t*, unsigned long long*, TableHdr*,
-                                    hipStream_t);
-hipError_t ytql_launch_strgrp_hash(const DevSeg*, const SegEx*, int, int,
-                                   const int64_t*, uint64_t*, uint64_t*,
-                                   ulonglong2*, int64_t, hipStream_t);
-hipError_t ytql_launch_strgrp_merge(const DevSeg*, const SegEx*, int, int,
-                                    const int64_t*, const unsigned long long*,
-                                    const uint64_t*, const uint64_t*,
-                                    const ulonglong2*, StrSlot*, uint64_t, int,
-                                    int, TableHdr*, int64_t, hipStream_t);
-hipError_t ytql_launch_strgrp_compact(const DevSeg*, const SegEx*, int,
-                                      const StrSlot*, uint64_t, OutStrGroup*,
-                                      unsigned long long*, char*, unsigned long long*,
-                                      uint64_t, TableHdr*, hipStream_t);
-hipError_t ytql_launch_strpred_entries(const DevSeg*, const SegEx*, int, int,
-                                       const int64_t*, int64_t, int, int,
-                                       const char*, int64_t, uint64_t*,
-                                       hipStream_t);
-hipError_t ytql_launch_inlist_str_entries(const DevSeg*, const SegEx*, int, int,
-                                          const int64_t*, int64_t,
-                                          const InStrSlot*, uint64_t, const char*,
-                                          int, uint64_t*, hipStream_t);
-hipError_t ytql_launch_strgen_accum(const DevPlan*, const DevSeg*, const SegEx*,
-                                    const int32_t*, const int32_t*, int, int64_t,
-                                    const int64_t*, unsigned long long*,
-                                    TableHdr*, unsigned*, hipStream_t);
-hipError_t ytql_launch_strgen_merge(const DevSeg*, const SegEx*, int, int,
-                                    const int64_t*, const unsigned long long*,
-                                    const StrGenAggs*, const uint64_t*,
-                                    const uint64_t*, const ulonglong2*,
-                                    StrSlot*, uint64_t, unsigned long long*,
-                                    TableHdr*, int64_t, hipStream_t);
-hipError_t ytql_launch_strgen_gather(OutStrGroup*, int64_t,
-                                     const unsigned long long*, uint64_t, int,
-                                     OutStrAgg*, int, int, hipStream_t);
-hipError_t ytql_launch_strst_count(const OutStrGroup*, int64_t, const char*,
-                                   int, unsigned long long*,
-                                   unsigned long long*, hipStream_t);
-hipError_t ytql_launch_strst_scatter(const OutStrGroup*, int64_t, const char*,
-                                     int, int, unsigned long long*,
-                                     unsigned long long*, YtStateRow*, char*,
-                                     const unsigned long long*, hipStream_t);
-hipError_t ytql_launch_strst_hash(const YtStateRow*, int64_t, const int64_t*,
-                                  const unsigned long long*, int, const char*,
-                                  uint64_t*, uint64_t*, ulonglong2*,
-                                  uint64_t*, hipStream_t);
-hipError_t ytql_launch_strst_merge(const YtStateRow*, int64_t, const char*,
-                                   const uint64_t*, const uint64_t*,
-                                   const ulonglong2*, const uint64_t*, int,
-                                   StrSlot*, uint64_t, TableHdr*, hipStream_t);
-hipError_t ytql_launch_strst_compact(const StrSlot*, uint64_t,
-                                     const uint64_t*, const char*,
-                                     OutStrState*, unsigned long long*,
-                                     char*, unsigned long long*, uint64_t,
-                                     TableHdr*, hipStream_t);
-}
 
 /* must match kernels.hip mix64 and the oracle's splitmix64 */
 static inline uint64_t splitmix64_host(uint64_t x)
@@ -627,7 +473,15 @@ static int in_num_prepare(const YtExpr* e, uint8_t vt, InNumSet* s,
 }
 
 static int emit_inst(DevPlan* p, int op, int col, uint64_t bits,
-                     char* errbuf, size_t errlen);
+                     char* errbuf, size_t errlen)
+{
+    if (p->prog_len >= kMaxProg) { set_err(errbuf, errlen, "expression too long"); return YT_ERR_INVALID_PLAN; }
+    PInst& in = p->prog[p->prog_len++];
+    in.op = op;
+    in.col = col;
+    in.bits = bits;
+    return YT_OK;
+}
 
 /* numeric YT_EX_IN: the operand's program, then one P_IN_NUM */
 static int compile_in_num(const YtExpr* e, DevPlan* p, StrPreds* sp, int* len,
@@ -740,17 +594,6 @@ extern "C" int yt_strpred_eval(int op, int escape, const char* text,
         if (strpred_like_bad_pattern(lit, lit_len, escape)) return -2;
     }
     return strpred_eval(op, escape, text, text_len, lit, lit_len);
-}
-
-static int emit_inst(DevPlan* p, int op, int col, uint64_t bits,
-                     char* errbuf, size_t errlen)
-{
-    if (p->prog_len >= kMaxProg) { set_err(errbuf, errlen, "expression too long"); return YT_ERR_INVALID_PLAN; }
-    PInst& in = p->prog[p->prog_len++];
-    in.op = op;
-    in.col = col;
-    in.bits = bits;
-    return YT_OK;
 }
 
 static bool is_string_col(const YtExpr* e, const DevPlan* p)
@@ -4294,10 +4137,6 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
     sp.tile_rows = 8192;
     if (sp.tile_rows > rows0) sp.tile_rows = rows0 > 256 ? rows0 : 256;
     sp.tiles_per_seg = (rows0 + sp.tile_rows - 1) / sp.tile_rows;
-    {
-        const char* sa = getenv("YTQL_STRACCUM");
-        sp.xcd_affine = sa ? atoi(sa) : 1;
-    }
     const int32_t last_rows = R.h_segs[koff + knseg - 1].row_count;
     sp.ntiles = (knseg - 1) * sp.tiles_per_seg
               + (last_rows + sp.tile_rows - 1) / sp.tile_rows;
@@ -4315,14 +4154,11 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
     HIP_CHECK(hipMemsetAsync(d_acc, 0, sizeof(uint64_t) * acc_stride * (total_dict ? total_dict : 1), R.stream));
     HIP_CHECK(ps.dev(&d_hashes, sizeof(uint64_t) * (total_dict ? total_dict : 1)));
     /* per-entry identity + prefix arrays: filled by the hash kernel so
-     * the merge's hot path reads them as a stream (YTQL_STRMERGE=0
-     * falls back to the round-1 dict-read probe for A/B) */
+     * the merge's hot path reads them as a stream */
     uint64_t* d_idents = nullptr;
     ulonglong2* d_pfxs = nullptr;
     HIP_CHECK(ps.dev(&d_idents, sizeof(uint64_t) * (total_dict ? total_dict : 1)));
     HIP_CHECK(ps.dev(&d_pfxs, sizeof(ulonglong2) * (total_dict ? total_dict : 1)));
-    const char* sm_env = getenv("YTQL_STRMERGE");
-    const int merge_fast = sm_env ? atoi(sm_env) : 1;
     /* Table sized for the worst case (every dict entry distinct).
      * Measured: an 8×-smaller table holding just the ~6 M live keys is
      * NOT faster — the merge's scattered atomics then fight over hot
@@ -4335,15 +4171,13 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
     /* Start smaller than the every-entry-distinct worst case: the 64 B/slot
      * table is memset before the merge and scanned by the compact, so an
      * oversized table costs real milliseconds per step. With a caller
-     * hint, 2x the hint; otherwise half the entry count (cross-segment
-     * duplication >= 2x in any chunk where a GROUP BY is the right
-     * plan). The grow-on-overflow loop below keeps correctness for
+     * hint, kSlotsPerHintedGroup x the hint; otherwise half the entry count
+     * (cross-segment duplication >= 2x in any chunk where a GROUP BY is the
+     * right plan). The grow-on-overflow loop below keeps correctness for
      * adversarial cardinalities (one 4x retry reaches 2x entries). */
-    const char* sx_env = getenv("YTQL_STRSLOTS_X");
-    uint64_t slots_x = sx_env ? (uint64_t)atoll(sx_env) : 4;
-    if (slots_x < 1) slots_x = 1;
+    constexpr uint64_t kSlotsPerHintedGroup = 4;
     uint64_t nslots = options->max_groups_hint > 0
-        ? next_pow2((uint64_t)options->max_groups_hint * slots_x)
+        ? next_pow2((uint64_t)options->max_groups_hint * kSlotsPerHintedGroup)
         : next_pow2((uint64_t)(total_dict ? total_dict : 1) / 2 + 1);
     if (nslots < 2048) nslots = 2048;
     if (nslots > nslots_cap) nslots = nslots_cap;
@@ -4400,8 +4234,7 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
                                                d_accbase, d_acc, d_hashes,
                                                d_idents, d_pfxs,
                                                d_slots, nslots, val_is_double,
-                                               merge_fast, R.d_th, total_dict,
-                                               R.stream));
+                                               R.d_th, total_dict, R.stream));
         }
         HIP_CHECK(hipMemcpy(&th, R.d_th, sizeof(th), hipMemcpyDeviceToHost));
         if (th.overflow != 1 || nslots >= nslots_cap) break;

@@ -26,6 +26,7 @@
 #include "common.h"
 #include "strpred.h"
 #include "inlist.h"
+#include "launch.h"
 #include "../../include/ytql_gpu.h"
 
 namespace ytql {
@@ -2706,7 +2707,7 @@ k_strgrp_accum(StrGroupParams sp, const DevSeg* segs, const SegEx* segex,
      * ALL tiles of a segment — and therefore all atomics into its ~1.3 MB
      * accumulator region — inside one XCD's 4 MB L2 instead of ping-ponging
      * the lines across eight of them. */
-    const bool affine = sp.xcd_affine && gridDim.x >= 64;
+    const bool affine = gridDim.x >= 64;
     const int xcd = blockIdx.x & 7;
     const int sub = blockIdx.x >> 3;
     const int nsub = gridDim.x >> 3;
@@ -2822,11 +2823,257 @@ k_strgrp_accum(StrGroupParams sp, const DevSeg* segs, const SegEx* segex,
     }
 }
 
-/* S2: FNV-1a hash of every dictionary entry. Also materializes the per-entry
- * slot identity (hash48|len) and 16-byte prefix that the merge compares
- * against StrSlot.ident/pfx — this kernel already streams every dictionary
- * byte, so capturing them here lets the merge's hot path touch ONLY its
- * streaming arrays and the slot line (no dict reads, no binary search). */
+/* ---- shared by every string-key merge (common.h StrSlot) ---- */
+
+__device__ __forceinline__ uint64_t fnv1a_bytes(const char* p, uint32_t len)
+{
+    uint64_t h = 0xCBF29CE484222325ULL;
+    for (uint32_t k = 0; k < len; k++)
+        h = (h ^ (uint8_t)p[k]) * 0x100000001B3ULL;
+    return h;
+}
+
+/* the segment that owns global entry g: the last s with base[s] <= g */
+__device__ __forceinline__ int seg_of(const int64_t* base, int nsegs, int64_t g)
+{
+    int lo = 0, hi = nsegs;
+    while (lo + 1 < hi) {
+        int mid = (lo + hi) / 2;
+        if (base[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+/* what the merges stream per key: the FNV-1a hash, the slot identity
+ * (hash48|len16) and the first 16 bytes, zero-padded */
+__device__ __forceinline__ void str_key_identity(const char* p, uint32_t len,
+                                                 uint64_t* hash, uint64_t* ident,
+                                                 ulonglong2* pfx)
+{
+    const uint64_t h = fnv1a_bytes(p, len);
+    ulonglong2 pf;
+    pf.x = 0; pf.y = 0;
+    const uint32_t npfx = len < 16 ? len : 16;
+    for (uint32_t k = 0; k < npfx; k++)
+        ((char*)&pf)[k] = p[k];
+    *hash = h;
+    *ident = ((h >> 16) << 16) | (uint64_t)(len & 0xFFFF);
+    *pfx = pf;
+}
+
+/* exclusive scan of (a, b) over the 256 threads of a block, in thread
+ * order; *ta, *tb = the block totals (the same in every thread) */
+__device__ __forceinline__ void block_excl_scan2(uint64_t& a, uint64_t& b,
+                                                 uint64_t* ta, uint64_t* tb,
+                                                 uint64_t (*wsum)[2] /* [4] LDS */)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t ia = a, ib = b;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t xa = (uint64_t)__shfl_up((unsigned long long)ia, d, 64);
+        const uint64_t xb = (uint64_t)__shfl_up((unsigned long long)ib, d, 64);
+        if (lane >= d) { ia += xa; ib += xb; }
+    }
+    __syncthreads();            /* wsum may still be read from the last call */
+    if (lane == 63) { wsum[wave][0] = ia; wsum[wave][1] = ib; }
+    __syncthreads();
+    uint64_t ba = 0, bb = 0, sa = 0, sb = 0;
+    for (int w = 0; w < 4; w++) {
+        if (w < wave) { ba += wsum[w][0]; bb += wsum[w][1]; }
+        sa += wsum[w][0];
+        sb += wsum[w][1];
+    }
+    a = ba + ia - a;
+    b = bb + ib - b;
+    *ta = sa;
+    *tb = sb;
+}
+
+/* The slot identity protocol, once. Find the slot that holds key's string
+ * or claim an empty one for it; nullptr when the probe gave up (table too
+ * small: the caller raises th->overflow and the host retries at 4x, never a
+ * wrong result). *claimed = this call created the group.
+ *
+ * Everything the hot path needs is STREAMED (hash, ident, pfx are read in
+ * key order) — the only random memory is the slot line itself, read as ONE
+ * 32-byte load (rep|ident|pfx share the line's first half). What a Key
+ * resolves lazily — its claim word, the owner's bytes — is paid only by the
+ * ~1/dup-factor claimers and the rare fallbacks.
+ *
+ * A Key supplies:
+ *   hash(), ident(), pfx()  from the streamed arrays
+ *   rep()                   the nonzero claim word that names this key,
+ *                           computed on first use and cached
+ *   equals_owner(cur)       exact: are this key's bytes those of the key
+ *                           that claim word cur names */
+template <typename Key>
+__device__ __forceinline__ StrSlot* strslot_find_or_claim(StrSlot* slots, uint64_t mask,
+                                                          Key& key, bool* claimed)
+{
+    const uint64_t h = key.hash();
+    const uint64_t my_ident = key.ident();
+    const uint32_t my_len = (uint32_t)(my_ident & 0xFFFF);
+    const ulonglong2 pf = key.pfx();
+    *claimed = false;
+    uint64_t sidx = mix64(h) & mask;
+    /* probe chains this long only happen when the table is (nearly) full —
+     * give up early so a too-small table overflows in bounded time */
+    const uint64_t max_probe = mask < 8192 ? mask : 8192;
+    for (uint64_t it = 0; it <= max_probe; it++, sidx = (sidx + 1) & mask) {
+        StrSlot* cand = &slots[sidx];
+        const ulonglong4 v = *(const ulonglong4*)cand;
+        unsigned long long cur = v.x;
+        uint64_t oident = v.y;
+        if (cur == 0ULL) {
+            cur = atomicCAS(&cand->rep, 0ULL, key.rep());
+            if (cur == 0ULL) {
+                /* claimed: publish the identity (relaxed agent stores;
+                 * readers that catch it unpublished fall back to the exact
+                 * compare) */
+                __hip_atomic_store(&cand->pfx[0], pf.x,
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&cand->pfx[1], pf.y,
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&cand->ident, my_ident,
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                *claimed = true;
+                return cand;
+            }
+            /* lost the race: cand belongs to someone else now and its
+             * identity may be unpublished — treat as oident 0 */
+            oident = 0;
+        }
+        if (oident != 0 && oident != my_ident) continue;
+        if (oident == my_ident && my_len <= 16
+            && v.z == pf.x && v.w == pf.y) return cand;
+        /* unpublished identity, long key, or prefix mismatch on an ident
+         * match: decide exactly from the owner's bytes (rare) */
+        if (key.equals_owner(cur)) return cand;
+    }
+    return nullptr;
+}
+
+/* Key: global dictionary entry g of the key column. rep = (seg+1)<<32 |
+ * 1-based id in that segment. The segment search is lazy: only claimers
+ * and fallbacks pay it (and the dictionary reads behind it). kEagerRep runs
+ * it in the constructor instead, where it overlaps the streamed loads:
+ * k_strgen_merge's choice, about 4 % faster there at one claimer in five
+ * entries (profiles/r06); k_strgrp_merge keeps the lazy form config 5 was tuned on. */
+template <bool kEagerRep>
+struct DictEntryKey {
+    const DevSeg* segs;
+    const SegEx* segex;
+    int key_seg_off, nsegs;
+    const int64_t* acc_base;
+    const uint64_t* hashes;
+    const uint64_t* idents;
+    const ulonglong2* pfxs;
+    int64_t g;
+    uint64_t h;
+    int seg;                        /* valid once rep_ != 0 */
+    unsigned long long rep_;
+
+    __device__ __forceinline__
+    DictEntryKey(const DevSeg* segs_, const SegEx* segex_, int key_seg_off_,
+                 int nsegs_, const int64_t* acc_base_, const uint64_t* hashes_,
+                 const uint64_t* idents_, const ulonglong2* pfxs_, int64_t g_)
+        : segs(segs_), segex(segex_), key_seg_off(key_seg_off_), nsegs(nsegs_),
+          acc_base(acc_base_), hashes(hashes_), idents(idents_), pfxs(pfxs_),
+          g(g_), h(hashes_[g_]), seg(0), rep_(0)
+    {
+        if (kEagerRep) (void)rep();
+    }
+
+    __device__ __forceinline__ uint64_t hash() const { return h; }
+    __device__ __forceinline__ uint64_t ident() const { return idents[g]; }
+    __device__ __forceinline__ ulonglong2 pfx() const { return pfxs[g]; }
+    __device__ __forceinline__ unsigned long long rep()
+    {
+        if (!rep_) {
+            seg = seg_of(acc_base, nsegs, g);
+            rep_ = ((unsigned long long)(seg + 1) << 32)
+                 | (unsigned long long)(g - acc_base[seg] + 1);
+        }
+        return rep_;
+    }
+    __device__ __forceinline__ bool equals_owner(unsigned long long cur)
+    {
+        const int oseg = (int)(cur >> 32) - 1;
+        const int64_t oid = (int64_t)(cur & 0xFFFFFFFFULL);
+        if (hashes[acc_base[oseg] + oid - 1] != h) return false;
+        (void)rep();
+        uint32_t mlen, olen;
+        const char* mp = dict_entry(segs[key_seg_off + seg], segex[key_seg_off + seg],
+                                    g - acc_base[seg], &mlen);
+        const char* op = dict_entry(segs[key_seg_off + oseg],
+                                    segex[key_seg_off + oseg], oid - 1, &olen);
+        if (olen != mlen) return false;
+        uint32_t k = 0;
+        while (k < mlen && op[k] == mp[k]) k++;
+        return k == mlen;
+    }
+};
+
+/* Key: exchanged state i, its bytes in the concatenated pool at absoff[i]
+ * (offset << 24 | length). rep = i + 1. */
+struct PoolStateKey {
+    const char* pool;
+    const uint64_t* absoff;
+    const uint64_t* hashes;
+    const uint64_t* idents;
+    const ulonglong2* pfxs;
+    int64_t i;
+    uint64_t h;
+
+    __device__ __forceinline__
+    PoolStateKey(const char* pool_, const uint64_t* absoff_, const uint64_t* hashes_,
+                 const uint64_t* idents_, const ulonglong2* pfxs_, int64_t i_)
+        : pool(pool_), absoff(absoff_), hashes(hashes_), idents(idents_),
+          pfxs(pfxs_), i(i_), h(hashes_[i_]) {}
+
+    __device__ __forceinline__ uint64_t hash() const { return h; }
+    __device__ __forceinline__ uint64_t ident() const { return idents[i]; }
+    __device__ __forceinline__ ulonglong2 pfx() const { return pfxs[i]; }
+    __device__ __forceinline__ unsigned long long rep() const
+    {
+        return (unsigned long long)(i + 1);
+    }
+    __device__ __forceinline__ bool equals_owner(unsigned long long cur) const
+    {
+        const int64_t oi = (int64_t)cur - 1;
+        if (hashes[oi] != h) return false;
+        const uint64_t mab = absoff[i], oab = absoff[oi];
+        const uint32_t mlen = (uint32_t)(mab & 0xFFFFFF);
+        if ((uint32_t)(oab & 0xFFFFFF) != mlen) return false;
+        const char* mp = pool + (mab >> 24);
+        const char* op = pool + (oab >> 24);
+        uint32_t k = 0;
+        while (k < mlen && op[k] == mp[k]) k++;
+        return k == mlen;
+    }
+};
+
+/* Claims are counted per block in LDS (*s_claims) and folded into
+ * th->ngroups ONCE per block — a per-claim global atomicAdd on that single
+ * address serializes (~160 M/s measured, tools/probe_strcompact) and
+ * throttled the whole merge at 100 M distinct keys. The group-limit check
+ * sits on the fold. Every thread of the block calls this, after its loop. */
+__device__ __forceinline__ void strslot_fold_claims(const unsigned long long* s_claims,
+                                                    TableHdr* th)
+{
+    __syncthreads();
+    if (threadIdx.x == 0 && *s_claims) {
+        unsigned long long t = atomicAdd(&th->ngroups, *s_claims);
+        if (th->group_limit > 0 && (int64_t)(t + *s_claims) > th->group_limit)
+            mark_group_limit(th);
+    }
+}
+
+/* S2: hash, slot identity and 16-byte prefix of every dictionary entry. This
+ * kernel already streams every dictionary byte, so capturing them here lets
+ * the merge's hot path touch ONLY its streaming arrays and the slot line
+ * (no dict reads, no binary search). */
 __global__ void k_strgrp_hash(const DevSeg* segs, const SegEx* segex,
                               int key_seg_off, int nsegs,
                               const int64_t* acc_base, uint64_t* hashes,
@@ -2835,34 +3082,16 @@ __global__ void k_strgrp_hash(const DevSeg* segs, const SegEx* segex,
     int64_t total = acc_base[nsegs];
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
          g < total; g += (int64_t)gridDim.x * blockDim.x) {
-        int lo = 0, hi = nsegs;
-        while (lo + 1 < hi) {
-            int mid = (lo + hi) / 2;
-            if (acc_base[mid] <= g) lo = mid;
-            else hi = mid;
-        }
-        const DevSeg& sk = segs[key_seg_off + lo];
-        const SegEx& ek = segex[key_seg_off + lo];
+        const int s = seg_of(acc_base, nsegs, g);
         uint32_t len;
-        const char* p = dict_entry(sk, ek, g - acc_base[lo], &len);
-        uint64_t h = 0xCBF29CE484222325ULL;
-        for (uint32_t k = 0; k < len; k++) {
-            h = (h ^ (uint8_t)p[k]) * 0x100000001B3ULL;
-        }
-        hashes[g] = h;
-        idents[g] = ((h >> 16) << 16) | (uint64_t)(len & 0xFFFF);
-        ulonglong2 pf;
-        pf.x = 0; pf.y = 0;
-        uint32_t npfx = len < 16 ? len : 16;
-        for (uint32_t k = 0; k < npfx; k++)
-            ((char*)&pf)[k] = p[k];
-        pfxs[g] = pf;
+        const char* p = dict_entry(segs[key_seg_off + s], segex[key_seg_off + s],
+                                   g - acc_base[s], &len);
+        str_key_identity(p, len, &hashes[g], &idents[g], &pfxs[g]);
     }
 }
 
 /* S3: merge dictionary entries across segments by exact string identity.
- * One thread per dictionary entry with a nonzero count. Identity test:
- * hash gate (precomputed array, no publication race) then byte compare. */
+ * One thread per dictionary entry with a nonzero count. */
 __global__ void k_strgrp_merge(const DevSeg* segs, const SegEx* segex,
                                int key_seg_off, int nsegs,
                                const int64_t* acc_base,
@@ -2870,15 +3099,9 @@ __global__ void k_strgrp_merge(const DevSeg* segs, const SegEx* segex,
                                const uint64_t* hashes,
                                const uint64_t* idents, const ulonglong2* pfxs,
                                StrSlot* slots, uint64_t nslots,
-                               int val_is_double, int fast, TableHdr* th)
+                               int val_is_double, TableHdr* th)
 {
     int64_t total = acc_base[nsegs];
-    uint64_t mask = nslots - 1;
-    /* fast path: claims are counted per block in LDS and folded into
-     * th->ngroups ONCE per block — a per-claim global atomicAdd on that
-     * single address serializes (~160 M/s measured, tools/probe_strcompact)
-     * and throttled the whole merge at 100 M distinct keys. The group-limit
-     * check moves to the per-block fold (same flag, coarser timing). */
     __shared__ unsigned long long s_claims;
     if (threadIdx.x == 0) s_claims = 0;
     __syncthreads();
@@ -2886,198 +3109,12 @@ __global__ void k_strgrp_merge(const DevSeg* segs, const SegEx* segex,
          g < total; g += (int64_t)gridDim.x * blockDim.x) {
         unsigned long long cn = acc[2 * g];
         if (cn == 0) continue;
-        uint64_t h = hashes[g];
-        StrSlot* slot = nullptr;
-        if (fast) {
-            /* hot path: everything this entry needs is STREAMED (idents,
-             * pfxs, hashes, acc are read in entry order) — the only random
-             * memory is the slot line itself, read as ONE 32-byte load
-             * (rep|ident|pfx share the line's first half). The segment
-             * binary search and the dictionary-byte reads are resolved
-             * LAZILY: only the ~1/dup-factor claiming entries (and the rare
-             * hash48|len collisions) pay them. */
-            const uint64_t my_ident = idents[g];
-            const uint32_t my_len = (uint32_t)(my_ident & 0xFFFF);
-            const ulonglong2 pf = pfxs[g];
-            int lo = -1;
-            unsigned long long rep = 0;
-            uint64_t sidx = mix64(h) & mask;
-            uint64_t max_probe = mask < 8192 ? mask : 8192;
-            for (uint64_t it = 0; it <= max_probe; it++) {
-                StrSlot* cand = &slots[sidx];
-                ulonglong4 v = *(const ulonglong4*)cand;
-                unsigned long long cur = v.x;
-                uint64_t oident = v.y;
-                if (cur == 0ULL) {
-                    if (lo < 0) {
-                        int a = 0, b = nsegs;
-                        while (a + 1 < b) {
-                            int mid = (a + b) / 2;
-                            if (acc_base[mid] <= g) a = mid;
-                            else b = mid;
-                        }
-                        lo = a;
-                        rep = ((unsigned long long)(lo + 1) << 32)
-                            | (unsigned long long)(g - acc_base[lo] + 1);
-                    }
-                    cur = atomicCAS(&cand->rep, 0ULL, rep);
-                    if (cur == 0ULL) {
-                        __hip_atomic_store(&cand->pfx[0], pf.x,
-                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_store(&cand->pfx[1], pf.y,
-                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_store(&cand->ident, my_ident,
-                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        atomicAdd(&s_claims, 1ULL);
-                        slot = cand;
-                        break;
-                    }
-                    /* lost the race: cand belongs to someone else now and
-                     * its identity may be unpublished — treat as oident 0 */
-                    oident = 0;
-                }
-                if (oident != 0 && oident != my_ident) {
-                    sidx = (sidx + 1) & mask;
-                    continue;
-                }
-                if (oident == my_ident && my_len <= 16
-                    && v.z == pf.x && v.w == pf.y) { slot = cand; break; }
-                /* unpublished identity, long key, or prefix mismatch on an
-                 * ident match: decide exactly from the owner's dictionary
-                 * entry (rare) */
-                {
-                    int oseg = (int)(cur >> 32) - 1;
-                    int64_t oid = (int64_t)(cur & 0xFFFFFFFFULL);
-                    uint64_t oh = hashes[acc_base[oseg] + oid - 1];
-                    if (oh == h) {
-                        if (lo < 0) {
-                            int a = 0, b = nsegs;
-                            while (a + 1 < b) {
-                                int mid = (a + b) / 2;
-                                if (acc_base[mid] <= g) a = mid;
-                                else b = mid;
-                            }
-                            lo = a;
-                            rep = ((unsigned long long)(lo + 1) << 32)
-                                | (unsigned long long)(g - acc_base[lo] + 1);
-                        }
-                        uint32_t my_len2;
-                        const char* my_p = dict_entry(segs[key_seg_off + lo],
-                                                      segex[key_seg_off + lo],
-                                                      g - acc_base[lo], &my_len2);
-                        uint32_t olen;
-                        const char* op = dict_entry(segs[key_seg_off + oseg],
-                                                    segex[key_seg_off + oseg],
-                                                    oid - 1, &olen);
-                        if (olen == my_len2) {
-                            uint32_t k = 0;
-                            while (k < my_len2 && op[k] == my_p[k]) k++;
-                            if (k == my_len2) { slot = cand; break; }
-                        }
-                    }
-                }
-                sidx = (sidx + 1) & mask;
-            }
-            if (!slot) { th->overflow = 1; continue; }
-            atomicAdd((unsigned long long*)&slot->cnt, cn);
-            unsigned long long nn = cn >> 32;
-            if (nn) {
-                if (val_is_double)
-                    atomicAdd((double*)&slot->sum_bits,
-                              __longlong_as_double(acc[2 * g + 1]));
-                else
-                    atomicAdd((unsigned long long*)&slot->sum_bits, acc[2 * g + 1]);
-            }
-            continue;
-        }
-        int lo = 0, hi = nsegs;
-        while (lo + 1 < hi) {
-            int mid = (lo + hi) / 2;
-            if (acc_base[mid] <= g) lo = mid;
-            else hi = mid;
-        }
-        const DevSeg& my_s = segs[key_seg_off + lo];
-        const SegEx& my_e = segex[key_seg_off + lo];
-        int64_t my_id = g - acc_base[lo] + 1;
-        uint32_t my_len;
-        const char* my_p = dict_entry(my_s, my_e, my_id - 1, &my_len);
-        unsigned long long rep = ((unsigned long long)(lo + 1) << 32)
-                               | (unsigned long long)my_id;
-        /* in-slot identity (see common.h StrSlot): hash48|len + 16-byte
-         * prefix; a true duplicate resolves from the slot's own cache line
-         * instead of three scattered owner reads (the merge was 59% of the
-         * named config-5 step, fully latency-bound: WAIT_ANY 0.66 + 0.34) */
-        const uint64_t my_ident = ((h >> 16) << 16) | (uint64_t)(my_len & 0xFFFF);
-        uint64_t my_pfx[2] = {0, 0};
-        {
-            uint32_t npfx = my_len < 16 ? my_len : 16;
-            for (uint32_t k = 0; k < npfx; k++)
-                ((char*)my_pfx)[k] = my_p[k];
-        }
-
-        uint64_t sidx = mix64(h) & mask;
-        /* probe chains this long only happen when the table is (nearly)
-         * full — give up early so a too-small estimated table overflows in
-         * bounded time and the host retries at 4x (never a wrong result:
-         * overflow always surfaces as retry or YT_ERR_CAPACITY) */
-        uint64_t max_probe = mask < 8192 ? mask : 8192;
-        for (uint64_t it = 0; it <= max_probe; it++) {
-            StrSlot* cand = &slots[sidx];
-            unsigned long long cur = __hip_atomic_load(&cand->rep, __ATOMIC_RELAXED,
-                                                       __HIP_MEMORY_SCOPE_AGENT);
-            if (cur == 0ULL) {
-                cur = atomicCAS(&cand->rep, 0ULL, rep);
-                if (cur == 0ULL) {
-                    /* claimed: publish the identity (relaxed agent stores;
-                     * readers that catch it unpublished just fall back to
-                     * the exact owner-array compare) */
-                    __hip_atomic_store(&cand->pfx[0], my_pfx[0],
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&cand->pfx[1], my_pfx[1],
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&cand->ident, my_ident,
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    unsigned long long t = atomicAdd(&th->ngroups, 1ULL);
-                    if (th->group_limit > 0 && (int64_t)t >= th->group_limit)
-                        mark_group_limit(th);
-                    slot = cand;
-                    break;
-                }
-            }
-            if (cur == rep) { slot = cand; break; }
-            {
-                uint64_t oident = __hip_atomic_load(&cand->ident, __ATOMIC_RELAXED,
-                                                    __HIP_MEMORY_SCOPE_AGENT);
-                if (oident != 0) {
-                    if (oident != my_ident) { sidx = (sidx + 1) & mask; continue; }
-                    if (my_len <= 16) {
-                        uint64_t p0 = __hip_atomic_load(&cand->pfx[0], __ATOMIC_RELAXED,
-                                                        __HIP_MEMORY_SCOPE_AGENT);
-                        uint64_t p1 = __hip_atomic_load(&cand->pfx[1], __ATOMIC_RELAXED,
-                                                        __HIP_MEMORY_SCOPE_AGENT);
-                        if (p0 == my_pfx[0] && p1 == my_pfx[1]) { slot = cand; break; }
-                        /* prefix mismatch on a hash48|len match: either a
-                         * genuine collision or a not-yet-visible prefix —
-                         * decide exactly from the owner's dictionary entry */
-                    }
-                }
-                int oseg = (int)(cur >> 32) - 1;
-                int64_t oid = (int64_t)(cur & 0xFFFFFFFFULL);
-                uint64_t oh = hashes[acc_base[oseg] + oid - 1];
-                if (oh == h) {
-                    uint32_t olen;
-                    const char* op = dict_entry(segs[key_seg_off + oseg],
-                                                segex[key_seg_off + oseg], oid - 1, &olen);
-                    if (olen == my_len) {
-                        uint32_t k = 0;
-                        while (k < my_len && op[k] == my_p[k]) k++;
-                        if (k == my_len) { slot = cand; break; }
-                    }
-                }
-            }
-            sidx = (sidx + 1) & mask;
-        }
+        DictEntryKey<false> key(segs, segex, key_seg_off, nsegs, acc_base, hashes,
+                         idents, pfxs, g);
+        bool claimed;
+        StrSlot* slot = strslot_find_or_claim(slots, nslots - 1, key, &claimed);
         if (!slot) { th->overflow = 1; continue; }
+        if (claimed) atomicAdd(&s_claims, 1ULL);
         /* one packed atomic: cnt in the low half, nonnull in the high half
          * (both < 2^32 — segment row caps; carries cannot cross) */
         atomicAdd((unsigned long long*)&slot->cnt, cn);
@@ -3090,13 +3127,7 @@ __global__ void k_strgrp_merge(const DevSeg* segs, const SegEx* segex,
                 atomicAdd((unsigned long long*)&slot->sum_bits, acc[2 * g + 1]);
         }
     }
-    /* fold this block's claims (fast path; the slow path added per claim) */
-    __syncthreads();
-    if (threadIdx.x == 0 && s_claims) {
-        unsigned long long t = atomicAdd(&th->ngroups, s_claims);
-        if (th->group_limit > 0 && (int64_t)(t + s_claims) > th->group_limit)
-            mark_group_limit(th);
-    }
+    strslot_fold_claims(&s_claims, th);
 }
 
 /* S4: compact occupied slots; copy each group's key string into the device
@@ -3107,19 +3138,20 @@ __global__ void k_strgrp_merge(const DevSeg* segs, const SegEx* segex,
  * slot — while the raw 6.4 GB slot scan is 1.1 ms at 5.9 TB/s). So: each
  * block scans its contiguous slot range twice — pass A counts groups and
  * key bytes and claims space with ONE atomic pair per block, pass B emits
- * with an in-block (wave shfl scan + LDS cross-wave) prefix. */
-__global__ void k_strgrp_compact(const DevSeg* segs, const SegEx* segex,
-                                 int key_seg_off,
-                                 const StrSlot* slots, uint64_t nslots,
-                                 OutStrGroup* out, unsigned long long* counter,
-                                 char* pool, unsigned long long* pool_cursor,
-                                 uint64_t pool_cap, TableHdr* th)
+ * in slot order with an in-block prefix per 256-slot tile.
+ *   src.bytes(rep, &len)            the key bytes of the slot's owner
+ *   wr.write(idx, off_len, slot)    output record idx; key at off_len
+ * 256 threads per block (block_excl_scan2). */
+template <typename Src, typename Writer>
+__device__ __forceinline__ void strslot_compact(const StrSlot* slots, uint64_t nslots,
+                                                const Src& src, const Writer& wr,
+                                                unsigned long long* counter,
+                                                char* pool,
+                                                unsigned long long* pool_cursor,
+                                                uint64_t pool_cap, TableHdr* th)
 {
-    const int lane = threadIdx.x & 63;
-    const int wid = (int)(threadIdx.x >> 6);
-    const int nw = (int)(blockDim.x >> 6);
-    __shared__ unsigned long long s_wcnt[16], s_wlen[16];
-    __shared__ unsigned long long s_cbase, s_pbase, s_crun, s_lrun;
+    __shared__ uint64_t wsum[4][2];
+    __shared__ unsigned long long s_cbase, s_pbase;
 
     uint64_t per = (nslots + gridDim.x - 1) / gridDim.x;
     uint64_t b0 = (uint64_t)blockIdx.x * per;
@@ -3128,86 +3160,90 @@ __global__ void k_strgrp_compact(const DevSeg* segs, const SegEx* segex,
     if (b1 > nslots) b1 = nslots;
 
     /* pass A: count occupied slots + total key bytes in [b0, b1) */
-    unsigned long long c = 0, l = 0;
+    uint64_t c = 0, l = 0, tc, tl;
     for (uint64_t i = b0 + threadIdx.x; i < b1; i += blockDim.x) {
         unsigned long long rep = slots[i].rep;
         if (rep) {
-            int seg = (int)(rep >> 32) - 1;
-            int64_t id = (int64_t)(rep & 0xFFFFFFFFULL);
             uint32_t len;
-            (void)dict_entry(segs[key_seg_off + seg], segex[key_seg_off + seg],
-                             id - 1, &len);
+            (void)src.bytes(rep, &len);
             c++;
             l += len;
         }
     }
-    #pragma unroll
-    for (int d = 32; d; d >>= 1) {
-        c += __shfl_down(c, d, 64);
-        l += __shfl_down(l, d, 64);
-    }
-    if (lane == 0) { s_wcnt[wid] = c; s_wlen[wid] = l; }
-    __syncthreads();
+    block_excl_scan2(c, l, &tc, &tl, wsum);
     if (threadIdx.x == 0) {
-        unsigned long long tc = 0, tl = 0;
-        for (int w = 0; w < nw; w++) { tc += s_wcnt[w]; tl += s_wlen[w]; }
-        s_cbase = tc ? atomicAdd(counter, tc) : 0;
-        s_pbase = tl ? atomicAdd(pool_cursor, tl) : 0;
-        s_crun = 0;
-        s_lrun = 0;
+        s_cbase = tc ? atomicAdd(counter, (unsigned long long)tc) : 0;
+        s_pbase = tl ? atomicAdd(pool_cursor, (unsigned long long)tl) : 0;
     }
     __syncthreads();
-    const unsigned long long cbase = s_cbase, pbase = s_pbase;
+    uint64_t cbase = s_cbase, pbase = s_pbase;
 
-    /* pass B: ordered emit with an in-block prefix per tile */
+    /* pass B: ordered emit */
     for (uint64_t base = b0; base < b1; base += blockDim.x) {
         uint64_t i = base + threadIdx.x;
-        bool occ = false;
+        uint64_t occ = 0, off = 0;
         uint32_t len = 0;
         const char* p = nullptr;
-        const StrSlot* sl = nullptr;
         if (i < b1) {
-            sl = &slots[i];
-            unsigned long long rep = sl->rep;
+            unsigned long long rep = slots[i].rep;
             if (rep) {
-                occ = true;
-                int seg = (int)(rep >> 32) - 1;
-                int64_t id = (int64_t)(rep & 0xFFFFFFFFULL);
-                p = dict_entry(segs[key_seg_off + seg],
-                               segex[key_seg_off + seg], id - 1, &len);
+                occ = 1;
+                p = src.bytes(rep, &len);
+                off = len;
             }
         }
-        unsigned long long mask = __ballot(occ);
-        unsigned long long run = len;     /* inclusive wave scan of len */
-        #pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            unsigned long long v = __shfl_up(run, d, 64);
-            if (lane >= d) run += v;
-        }
-        if (lane == 63) { s_wcnt[wid] = __popcll(mask); s_wlen[wid] = run; }
-        __syncthreads();
+        uint64_t idx = occ;
+        block_excl_scan2(idx, off, &tc, &tl, wsum);
         if (occ) {
-            unsigned long long wc = 0, wl = 0;
-            for (int w = 0; w < wid; w++) { wc += s_wcnt[w]; wl += s_wlen[w]; }
-            unsigned long long off = pbase + s_lrun + wl + (run - len);
-            unsigned long long idx = cbase + s_crun + wc
-                + (unsigned long long)__popcll(mask & ((1ULL << lane) - 1));
+            idx += cbase;
+            off += pbase;
             if (off + len > pool_cap) {
                 th->overflow = 1;
             } else {
                 for (uint32_t k = 0; k < len; k++) pool[off + k] = p[k];
-                OutStrGroup& g = out[idx];
-                g.off_len = ((unsigned long long)off << 24) | len;
-                g.sum_bits = sl->sum_bits;
-                g.cnt_nonnull = sl->cnt;
+                wr.write(idx, ((unsigned long long)off << 24) | len, slots[i]);
             }
         }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int w = 0; w < nw; w++) { s_crun += s_wcnt[w]; s_lrun += s_wlen[w]; }
-        }
-        __syncthreads();
+        cbase += tc;
+        pbase += tl;
     }
+}
+
+struct DictEntrySrc {
+    const DevSeg* segs;
+    const SegEx* segex;
+    int key_seg_off;
+    __device__ __forceinline__ const char* bytes(unsigned long long rep,
+                                                 uint32_t* len) const
+    {
+        const int seg = (int)(rep >> 32) - 1;
+        const int64_t id = (int64_t)(rep & 0xFFFFFFFFULL);
+        return dict_entry(segs[key_seg_off + seg], segex[key_seg_off + seg],
+                          id - 1, len);
+    }
+};
+
+struct StrGroupWriter {
+    OutStrGroup* out;
+    __device__ __forceinline__ void write(uint64_t idx, unsigned long long off_len,
+                                          const StrSlot& sl) const
+    {
+        OutStrGroup& g = out[idx];
+        g.off_len = off_len;
+        g.sum_bits = sl.sum_bits;
+        g.cnt_nonnull = sl.cnt;
+    }
+};
+
+__global__ void __launch_bounds__(256)
+k_strgrp_compact(const DevSeg* segs, const SegEx* segex, int key_seg_off,
+                 const StrSlot* slots, uint64_t nslots,
+                 OutStrGroup* out, unsigned long long* counter,
+                 char* pool, unsigned long long* pool_cursor,
+                 uint64_t pool_cap, TableHdr* th)
+{
+    strslot_compact(slots, nslots, DictEntrySrc{segs, segex, key_seg_off},
+                    StrGroupWriter{out}, counter, pool, pool_cursor, pool_cap, th);
 }
 
 /* ------------------------------------------------------------------ */
@@ -3216,7 +3252,8 @@ __global__ void k_strgrp_compact(const DevSeg* segs, const SegEx* segex,
  * three stages as the specialised kernels above — dense per-(segment,
  * dictionary id) accumulators, identity merge into StrSlot, compact — with
  * a wider accumulator record and a per-slot aggregate array beside the
- * slot table. k_strgrp_hash and k_strgrp_compact are shared as they are. */
+ * slot table. k_strgrp_hash, the slot probe (strslot_find_or_claim over a
+ * DictEntryKey) and k_strgrp_compact are shared as they are. */
 
 /* 1-based dictionary id of row j of a string key segment; 0 = null key */
 __device__ __forceinline__ uint64_t str_key_id(const DevSeg& sk, const SegEx& ek,
@@ -3350,34 +3387,6 @@ k_inlist_str_entries(const DevSeg* segs, const SegEx* segex, int seg_off, int ns
 /* order and the scan is stable by construction.                        */
 
 constexpr int kProjRowsPerThread = kProjTile / 256;
-
-/* exclusive scan of (a, b) over the 256 threads of a block, in thread
- * order; *ta, *tb = the block totals (the same in every thread) */
-__device__ __forceinline__ void block_excl_scan2(uint64_t& a, uint64_t& b,
-                                                 uint64_t* ta, uint64_t* tb,
-                                                 uint64_t (*wsum)[2] /* [4] LDS */)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t ia = a, ib = b;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t xa = (uint64_t)__shfl_up((unsigned long long)ia, d, 64);
-        const uint64_t xb = (uint64_t)__shfl_up((unsigned long long)ib, d, 64);
-        if (lane >= d) { ia += xa; ib += xb; }
-    }
-    __syncthreads();            /* wsum may still be read from the last call */
-    if (lane == 63) { wsum[wave][0] = ia; wsum[wave][1] = ib; }
-    __syncthreads();
-    uint64_t ba = 0, bb = 0, sa = 0, sb = 0;
-    for (int w = 0; w < 4; w++) {
-        if (w < wave) { ba += wsum[w][0]; bb += wsum[w][1]; }
-        sa += wsum[w][0];
-        sb += wsum[w][1];
-    }
-    a = ba + ia - a;
-    b = bb + ib - b;
-    *ta = sa;
-    *tb = sb;
-}
 
 /* length of the entry a P_STR_REF value points at */
 __device__ __forceinline__ uint32_t str_ref_len(const DevSeg* segs, const SegEx* segex,
@@ -3635,90 +3644,14 @@ k_strgen_accum(DevPlan p, const DevSeg* segs, const SegEx* segex,
     }
 }
 
-/* find-or-claim the merge slot of dictionary entry g: the slot identity
- * protocol of k_strgrp_merge's streamed path (ident/pfx in-slot, exact
- * owner-entry compare as the fallback), as a function. k_strgrp_merge keeps
- * its own inlined copy: it is the measured config-5 hot loop and stays
- * byte-for-byte what was tuned. Returns nullptr when the probe gave up
- * (table too small); *claimed = 1 when this call created the group. */
-__device__ StrSlot* strgrp_find_slot(const DevSeg* segs, const SegEx* segex,
-                                     int key_seg_off, int nsegs,
-                                     const int64_t* acc_base, int64_t g,
-                                     const uint64_t* hashes,
-                                     const uint64_t* idents,
-                                     const ulonglong2* pfxs,
-                                     StrSlot* slots, uint64_t mask, int* claimed)
-{
-    const uint64_t h = hashes[g];
-    const uint64_t my_ident = idents[g];
-    const uint32_t my_len = (uint32_t)(my_ident & 0xFFFF);
-    const ulonglong2 pf = pfxs[g];
-    int lo = 0, hi = nsegs;
-    while (lo + 1 < hi) {
-        int mid = (lo + hi) / 2;
-        if (acc_base[mid] <= g) lo = mid;
-        else hi = mid;
-    }
-    const unsigned long long rep = ((unsigned long long)(lo + 1) << 32)
-                                 | (unsigned long long)(g - acc_base[lo] + 1);
-    *claimed = 0;
-    uint64_t sidx = mix64(h) & mask;
-    const uint64_t max_probe = mask < 8192 ? mask : 8192;
-    for (uint64_t it = 0; it <= max_probe; it++, sidx = (sidx + 1) & mask) {
-        StrSlot* cand = &slots[sidx];
-        unsigned long long cur = __hip_atomic_load(&cand->rep, __ATOMIC_RELAXED,
-                                                   __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == 0ULL) {
-            cur = atomicCAS(&cand->rep, 0ULL, rep);
-            if (cur == 0ULL) {
-                __hip_atomic_store(&cand->pfx[0], pf.x,
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&cand->pfx[1], pf.y,
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&cand->ident, my_ident,
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                *claimed = 1;
-                return cand;
-            }
-        }
-        if (cur == rep) return cand;
-        const uint64_t oident = __hip_atomic_load(&cand->ident, __ATOMIC_RELAXED,
-                                                  __HIP_MEMORY_SCOPE_AGENT);
-        if (oident != 0) {
-            if (oident != my_ident) continue;
-            if (my_len <= 16) {
-                uint64_t p0 = __hip_atomic_load(&cand->pfx[0], __ATOMIC_RELAXED,
-                                                __HIP_MEMORY_SCOPE_AGENT);
-                uint64_t p1 = __hip_atomic_load(&cand->pfx[1], __ATOMIC_RELAXED,
-                                                __HIP_MEMORY_SCOPE_AGENT);
-                if (p0 == pf.x && p1 == pf.y) return cand;
-            }
-        }
-        /* unpublished identity, long key, or prefix not visible yet: decide
-         * exactly from the owner's dictionary entry */
-        const int oseg = (int)(cur >> 32) - 1;
-        const int64_t oid = (int64_t)(cur & 0xFFFFFFFFULL);
-        if (hashes[acc_base[oseg] + oid - 1] != h) continue;
-        uint32_t mlen, olen;
-        const char* mp = dict_entry(segs[key_seg_off + lo], segex[key_seg_off + lo],
-                                    g - acc_base[lo], &mlen);
-        const char* op = dict_entry(segs[key_seg_off + oseg],
-                                    segex[key_seg_off + oseg], oid - 1, &olen);
-        if (olen != mlen) continue;
-        uint32_t k = 0;
-        while (k < mlen && op[k] == mp[k]) k++;
-        if (k == mlen) return cand;
-    }
-    return nullptr;
-}
-
 /* G2: fold every dictionary entry that kept at least one row into its
  * slot's aggregate record slot_aggs[stride * slot index] (same layout as
- * the accumulator record; counts are full 64-bit words). An entry whose
- * rows were all filtered out is skipped, so it creates no group. The
- * claimer leaves the slot's own index in StrSlot.sum_bits: k_strgrp_compact
- * copies that word into OutStrGroup.sum_bits, which is how k_strgen_gather
- * finds each compacted group's record. */
+ * the accumulator record; counts are full 64-bit words). The slot comes from
+ * the same strslot_find_or_claim over a DictEntryKey as in k_strgrp_merge.
+ * An entry whose rows were all filtered out is skipped, so it creates no
+ * group. The claimer leaves the slot's own index in StrSlot.sum_bits:
+ * k_strgrp_compact copies that word into OutStrGroup.sum_bits, which is how
+ * k_strgen_gather finds each compacted group's record. */
 __global__ void __launch_bounds__(256)
 k_strgen_merge(const DevSeg* segs, const SegEx* segex, int key_seg_off, int nsegs,
                const int64_t* acc_base, const unsigned long long* acc,
@@ -3735,10 +3668,10 @@ k_strgen_merge(const DevSeg* segs, const SegEx* segex, int key_seg_off, int nseg
          g < total; g += (int64_t)gridDim.x * blockDim.x) {
         const unsigned long long* rec = acc + (uint64_t)stride * (uint64_t)g;
         if (rec[0] == 0) continue;
-        int claimed;
-        StrSlot* slot = strgrp_find_slot(segs, segex, key_seg_off, nsegs, acc_base,
-                                         g, hashes, idents, pfxs, slots,
-                                         nslots - 1, &claimed);
+        DictEntryKey<true> key(segs, segex, key_seg_off, nsegs, acc_base, hashes,
+                         idents, pfxs, g);
+        bool claimed;
+        StrSlot* slot = strslot_find_or_claim(slots, nslots - 1, key, &claimed);
         if (!slot) { th->overflow = 1; continue; }
         const uint64_t sidx = (uint64_t)(slot - slots);
         if (claimed) {
@@ -3767,12 +3700,7 @@ k_strgen_merge(const DevSeg* segs, const SegEx* segex, int key_seg_off, int nseg
             atomicAdd(ap + 1, nn);
         }
     }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_claims) {
-        unsigned long long t = atomicAdd(&th->ngroups, s_claims);
-        if (th->group_limit > 0 && (int64_t)(t + s_claims) > th->group_limit)
-            mark_group_limit(th);
-    }
+    strslot_fold_claims(&s_claims, th);
 }
 
 /* G3: after k_strgrp_compact — fetch each compacted group's aggregate
@@ -3915,14 +3843,6 @@ __global__ void k_part_scatter(const OutGroup* groups, int64_t n, int nparts,
  * beside the states in the all-to-all. Partition = splitmix64(FNV-1a(key
  * bytes) [^ null marker]) % world — the byte-level mirror of
  * partition_hash, matching the oracle bit-for-bit. */
-__device__ __forceinline__ uint64_t fnv1a_bytes(const char* p, uint32_t len)
-{
-    uint64_t h = 0xCBF29CE484222325ULL;
-    for (uint32_t k = 0; k < len; k++)
-        h = (h ^ (uint8_t)p[k]) * 0x100000001B3ULL;
-    return h;
-}
-
 __global__ void k_strst_count(const OutStrGroup* groups, int64_t n,
                               const char* pool, int nparts,
                               unsigned long long* counts,
@@ -4016,39 +3936,25 @@ __global__ void k_strst_hash(const YtStateRow* states, int64_t n,
 {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
          i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        int lo = 0, hi = nsegin;
-        while (lo + 1 < hi) {
-            int mid = (lo + hi) / 2;
-            if (seg_row_base[mid] <= i) lo = mid;
-            else hi = mid;
-        }
+        const int s = seg_of(seg_row_base, nsegin, i);
         uint64_t ol = states[i].key_bits;
         uint32_t len = (uint32_t)(ol & 0xFFFFFF);
-        uint64_t ab = seg_pool_base[lo] + (ol >> 24);
+        uint64_t ab = seg_pool_base[s] + (ol >> 24);
         absoff[i] = (ab << 24) | len;
         if (states[i].meta & 1) { idents[i] = 0; hashes[i] = 0; continue; }
-        uint64_t h = fnv1a_bytes(pool + ab, len);
-        hashes[i] = h;
-        idents[i] = ((h >> 16) << 16) | (uint64_t)(len & 0xFFFF);
-        ulonglong2 pf;
-        pf.x = 0; pf.y = 0;
-        uint32_t npfx = len < 16 ? len : 16;
-        const char* p = pool + ab;
-        for (uint32_t k = 0; k < npfx; k++) ((char*)&pf)[k] = p[k];
-        pfxs[i] = pf;
+        str_key_identity(pool + ab, len, &hashes[i], &idents[i], &pfxs[i]);
     }
 }
 
-/* front-query merge over string states: StrSlot probe (rep = state index+1,
- * identity from the streamed arrays, exact compare against the owner's pool
- * bytes); counts are FULL u64 (slot->cnt = rows, slot->pad0_ = nonnull) */
+/* front-query merge over string states: strslot_find_or_claim over a
+ * PoolStateKey; counts are FULL u64 (slot->cnt = rows, slot->pad0_ =
+ * nonnull) */
 __global__ void k_strst_merge(const YtStateRow* states, int64_t n,
                               const char* pool, const uint64_t* hashes,
                               const uint64_t* idents, const ulonglong2* pfxs,
                               const uint64_t* absoff, int sum_slot,
                               StrSlot* slots, uint64_t nslots, TableHdr* th)
 {
-    uint64_t mask = nslots - 1;
     __shared__ unsigned long long s_claims;
     if (threadIdx.x == 0) s_claims = 0;
     __syncthreads();
@@ -4072,58 +3978,11 @@ __global__ void k_strst_merge(const YtStateRow* states, int64_t n,
             }
             continue;
         }
-        const uint64_t my_ident = idents[i];
-        const uint32_t my_len = (uint32_t)(my_ident & 0xFFFF);
-        const ulonglong2 pf = pfxs[i];
-        const uint64_t h = hashes[i];
-        const char* my_p = pool + (absoff[i] >> 24);
-        unsigned long long rep = (unsigned long long)(i + 1);
-        StrSlot* slot = nullptr;
-        uint64_t sidx = mix64(h) & mask;
-        uint64_t max_probe = mask < 8192 ? mask : 8192;
-        for (uint64_t it = 0; it <= max_probe; it++) {
-            StrSlot* cand = &slots[sidx];
-            ulonglong4 v = *(const ulonglong4*)cand;
-            unsigned long long cur = v.x;
-            uint64_t oident = v.y;
-            if (cur == 0ULL) {
-                cur = atomicCAS(&cand->rep, 0ULL, rep);
-                if (cur == 0ULL) {
-                    __hip_atomic_store(&cand->pfx[0], pf.x,
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&cand->pfx[1], pf.y,
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&cand->ident, my_ident,
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    atomicAdd(&s_claims, 1ULL);
-                    slot = cand;
-                    break;
-                }
-                oident = 0;
-            }
-            if (oident != 0 && oident != my_ident) {
-                sidx = (sidx + 1) & mask;
-                continue;
-            }
-            if (oident == my_ident && my_len <= 16
-                && v.z == pf.x && v.w == pf.y) { slot = cand; break; }
-            {
-                int64_t oi = (int64_t)cur - 1;
-                if (hashes[oi] == h) {
-                    uint64_t oab = absoff[oi];
-                    uint32_t olen = (uint32_t)(oab & 0xFFFFFF);
-                    uint64_t full_len = (uint32_t)(absoff[i] & 0xFFFFFF);
-                    if (olen == full_len) {
-                        const char* op = pool + (oab >> 24);
-                        uint32_t k = 0;
-                        while (k < olen && op[k] == my_p[k]) k++;
-                        if (k == olen) { slot = cand; break; }
-                    }
-                }
-            }
-            sidx = (sidx + 1) & mask;
-        }
+        PoolStateKey key(pool, absoff, hashes, idents, pfxs, i);
+        bool claimed;
+        StrSlot* slot = strslot_find_or_claim(slots, nslots - 1, key, &claimed);
         if (!slot) { th->overflow = 1; continue; }
+        if (claimed) atomicAdd(&s_claims, 1ULL);
         atomicAdd((unsigned long long*)&slot->cnt,
                   (unsigned long long)sr.row_count);
         if (sum_slot >= 0 && (sr.meta >> 8)) {
@@ -4137,106 +3996,46 @@ __global__ void k_strst_merge(const YtStateRow* states, int64_t n,
                       (unsigned long long)(sr.meta >> 8));
         }
     }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_claims) {
-        unsigned long long t = atomicAdd(&th->ngroups, s_claims);
-        if (th->group_limit > 0 && (int64_t)(t + s_claims) > th->group_limit)
-            mark_group_limit(th);
-    }
+    strslot_fold_claims(&s_claims, th);
 }
 
-/* compact the merged string-state table; strings come from the exchanged
- * pool via the owner state's absolute offset (two-pass block compaction
- * like k_strgrp_compact) */
-__global__ void k_strst_compact(const StrSlot* slots, uint64_t nslots,
-                                const uint64_t* absoff, const char* pool,
-                                OutStrState* out, unsigned long long* counter,
-                                char* out_pool, unsigned long long* pool_cursor,
-                                uint64_t pool_cap, TableHdr* th)
+/* compact the merged string-state table (strslot_compact); strings come from
+ * the exchanged pool via the owner state's absolute offset */
+struct PoolStateSrc {
+    const uint64_t* absoff;
+    const char* pool;
+    __device__ __forceinline__ const char* bytes(unsigned long long rep,
+                                                 uint32_t* len) const
+    {
+        const uint64_t ab = absoff[rep - 1];
+        *len = (uint32_t)(ab & 0xFFFFFF);
+        return pool + (ab >> 24);
+    }
+};
+
+struct StrStateWriter {
+    OutStrState* out;
+    __device__ __forceinline__ void write(uint64_t idx, unsigned long long off_len,
+                                          const StrSlot& sl) const
+    {
+        OutStrState& g = out[idx];
+        g.off_len = off_len;
+        g.sum_bits = sl.sum_bits;
+        g.cnt = sl.cnt;
+        g.nonnull = sl.pad0_;
+    }
+};
+
+__global__ void __launch_bounds__(256)
+k_strst_compact(const StrSlot* slots, uint64_t nslots,
+                const uint64_t* absoff, const char* pool,
+                OutStrState* out, unsigned long long* counter,
+                char* out_pool, unsigned long long* pool_cursor,
+                uint64_t pool_cap, TableHdr* th)
 {
-    const int lane = threadIdx.x & 63;
-    const int wid = (int)(threadIdx.x >> 6);
-    const int nw = (int)(blockDim.x >> 6);
-    __shared__ unsigned long long s_wcnt[16], s_wlen[16];
-    __shared__ unsigned long long s_cbase, s_pbase, s_crun, s_lrun;
-
-    uint64_t per = (nslots + gridDim.x - 1) / gridDim.x;
-    uint64_t b0 = (uint64_t)blockIdx.x * per;
-    if (b0 > nslots) b0 = nslots;
-    uint64_t b1 = b0 + per;
-    if (b1 > nslots) b1 = nslots;
-
-    unsigned long long c = 0, l = 0;
-    for (uint64_t i = b0 + threadIdx.x; i < b1; i += blockDim.x) {
-        unsigned long long rep = slots[i].rep;
-        if (rep) { c++; l += (uint32_t)(absoff[rep - 1] & 0xFFFFFF); }
-    }
-    #pragma unroll
-    for (int d = 32; d; d >>= 1) {
-        c += __shfl_down(c, d, 64);
-        l += __shfl_down(l, d, 64);
-    }
-    if (lane == 0) { s_wcnt[wid] = c; s_wlen[wid] = l; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long tc = 0, tl = 0;
-        for (int w = 0; w < nw; w++) { tc += s_wcnt[w]; tl += s_wlen[w]; }
-        s_cbase = tc ? atomicAdd(counter, tc) : 0;
-        s_pbase = tl ? atomicAdd(pool_cursor, tl) : 0;
-        s_crun = 0;
-        s_lrun = 0;
-    }
-    __syncthreads();
-    const unsigned long long cbase = s_cbase, pbase = s_pbase;
-
-    for (uint64_t base = b0; base < b1; base += blockDim.x) {
-        uint64_t i = base + threadIdx.x;
-        bool occ = false;
-        uint32_t len = 0;
-        const char* p = nullptr;
-        const StrSlot* sl = nullptr;
-        if (i < b1) {
-            sl = &slots[i];
-            unsigned long long rep = sl->rep;
-            if (rep) {
-                occ = true;
-                uint64_t ab = absoff[rep - 1];
-                len = (uint32_t)(ab & 0xFFFFFF);
-                p = pool + (ab >> 24);
-            }
-        }
-        unsigned long long mask = __ballot(occ);
-        unsigned long long run = len;     /* inclusive wave scan of len */
-        #pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            unsigned long long v = __shfl_up(run, d, 64);
-            if (lane >= d) run += v;
-        }
-        if (lane == 63) { s_wcnt[wid] = __popcll(mask); s_wlen[wid] = run; }
-        __syncthreads();
-        if (occ) {
-            unsigned long long wc = 0, wl = 0;
-            for (int w = 0; w < wid; w++) { wc += s_wcnt[w]; wl += s_wlen[w]; }
-            unsigned long long off = pbase + s_lrun + wl + (run - len);
-            unsigned long long idx = cbase + s_crun + wc
-                + (unsigned long long)__popcll(mask & ((1ULL << lane) - 1));
-            if (off + len > pool_cap) {
-                th->overflow = 1;
-            } else {
-                for (uint32_t k = 0; k < len; k++) out_pool[off + k] = p[k];
-                OutStrState& g = out[idx];
-                g.off_len = (off << 24) | len;
-                g.sum_bits = sl->sum_bits;
-                g.cnt = sl->cnt;
-                g.nonnull = sl->pad0_;
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int w = 0; w < nw; w++) { s_crun += s_wcnt[w]; s_lrun += s_wlen[w]; }
-        }
-        __syncthreads();
-    }
+    strslot_compact(slots, nslots, PoolStateSrc{absoff, pool},
+                    StrStateWriter{out}, counter, out_pool, pool_cursor,
+                    pool_cap, th);
 }
 
 /* merge state rows into a (fresh) table — front-query Merge semantics
@@ -4749,14 +4548,14 @@ hipError_t ytql_launch_strgrp_merge(const DevSeg* segs, const SegEx* segex,
                                     const uint64_t* hashes,
                                     const uint64_t* idents, const ulonglong2* pfxs,
                                     StrSlot* slots, uint64_t nslots,
-                                    int val_is_double, int fast, TableHdr* th,
+                                    int val_is_double, TableHdr* th,
                                     int64_t total, hipStream_t st)
 {
     int64_t want = (total + 255) / 256;
     int grid = (int)(want > 4096 ? 4096 : (want ? want : 1));
     hipLaunchKernelGGL(k_strgrp_merge, dim3(grid), dim3(256), 0, st,
                        segs, segex, key_seg_off, nsegs, acc_base, acc, hashes,
-                       idents, pfxs, slots, nslots, val_is_double, fast, th);
+                       idents, pfxs, slots, nslots, val_is_double, th);
     return hipGetLastError();
 }
 
