@@ -160,6 +160,19 @@ __device__ __forceinline__ uint64_t bp_gl(const uint64_t* base, uint64_t mask,
     return (lo | hi) & mask;
 }
 
+/* the same from n words staged in LDS; never reads past them: a value that
+ * ends in the last word takes nothing from the clamped one */
+__device__ __forceinline__ uint64_t bp_lds(const uint64_t* words, uint32_t n, uint64_t mask,
+                                           uint32_t width, uint32_t index)
+{
+    const uint32_t bit = index * width;
+    const unsigned off = bit & 63;
+    const uint32_t wi = bit >> 6;
+    const uint64_t lo = words[wi] >> off;
+    const uint64_t hi = (words[wi + 1 < n ? wi + 1 : wi] << 1) << (63 - off);
+    return (lo | hi) & mask;
+}
+
 /* ------------------------------------------------------------------ */
 /* segment header parsing (one thread per segment)                     */
 
@@ -2110,19 +2123,24 @@ constexpr unsigned kRowNullVal = 0x40000000u;   /* goes to the null-value stream
  *      then rank each row in its bucket with a returning LDS add;
  *   3. one block scan of the histogram gives each bucket's offset in the
  *      tile, one global add per non-empty bucket reserves its run in the
- *      (bucket, XCD sub) region;
- *   4. records go to an LDS scratch at off[b] + rank, bucket-major;
+ *      (bucket, XCD sub) region. The cursors lie [sub][bucket], so a
+ *      wave's adds fall on 1 KiB of adjacent words, and they are only
+ *      ISSUED here;
+ *   4. records go to an LDS scratch at off[b] + rank, bucket-major, while
+ *      the adds are in flight; then their returned bases give delta[] and
+ *      the capacity guard, which gates step 5 alone;
  *   5. the scratch is copied out with every lane busy: lane r re-derives
  *      its record's bucket and stores to base[b] + (r - off[b]), so a
  *      bucket's run leaves as contiguous stores from adjacent lanes.
- * Null-value rows (key only, rare) go straight to their own stream. */
+ * Null-value rows (key only, rare) go straight to their own stream, from
+ * registers, in step 5. */
 template <bool PACKED>
 __global__ void __launch_bounds__(kPartThreads, 4)
 k_scan_partition(PartParams pp, const DevSeg* segs, const SegEx* segex,
                  const FastCol* cols, TableHdr* th,
-                 unsigned long long* cursors,        /* kNB x 8 main */
+                 unsigned long long* cursors,        /* 8 x kNB main: [sub][bucket] */
                  ulonglong2* recs,
-                 unsigned long long* ncursors,       /* kNB x 8 null-value stream */
+                 unsigned long long* ncursors,       /* 8 x kNB null-value stream */
                  uint64_t* nrecs)
 {
     constexpr int R = (PACKED ? kPartTileMax : kPartTileMin) / kPartThreads;
@@ -2145,14 +2163,14 @@ k_scan_partition(PartParams pp, const DevSeg* segs, const SegEx* segex,
     const uint64_t recmask = (pp.bits_k >= 64) ? ~0ULL : ((1ULL << pp.bits_k) - 1);
     uint64_t* recs8 = (uint64_t*)recs;
 
-    for (int tile = blockIdx.x; tile < pp.ntiles; tile += gridDim.x) {
+    for (int tile = blockIdx.x, half = 0; tile < pp.ntiles; ) {
         const int seg_idx = tile / pp.tiles_per_seg;
         const int tile_in_seg = tile % pp.tiles_per_seg;
-        const int64_t t0 = (int64_t)tile_in_seg * pp.tile_rows;
+        const int64_t ts = (int64_t)tile_in_seg * pp.tile_rows;
         const int32_t seg_rows = segs[cols[1].seg_off + seg_idx].row_count;
-        if (t0 >= seg_rows) continue;   /* a tile past a short segment's end */
-        int64_t t1 = t0 + pp.tile_rows;   /* <= R rows per thread */
-        if (t1 > seg_rows) t1 = seg_rows;
+        if (ts >= seg_rows) { tile += gridDim.x; continue; }   /* a tile past a short segment's end */
+        int64_t te = ts + pp.tile_rows;   /* <= R rows per thread */
+        if (te > seg_rows) te = seg_rows;
 
         const uint64_t* fwords = nullptr;
         const uint8_t* fbm = nullptr;
@@ -2191,34 +2209,79 @@ k_scan_partition(PartParams pp, const DevSeg* segs, const SegEx* segex,
                 vbm = (const uint8_t*)sg.blob + e.off_bitmap_bytes;
         }
 
+        /* The tile's packed key and value words are staged in the scratch,
+         * which is idle until step 4. A tile of kw + vw bits per row fits the
+         * 64 KiB whenever its records do; where a segment is written wider
+         * than its column's span and a large tile does not fit, the tile is
+         * taken as two small ones, which always fit: its second half is the
+         * loop's next turn. */
+        int64_t step = pp.tile_rows;
+        {
+            const uint32_t n = (uint32_t)(te - ts);
+            if ((((n * kwd + 63) >> 6) + 1 & ~1u) + (((n * vwd + 63) >> 6) + 1 & ~1u) > kPartScratchBytes / 8)
+                step = kPartTileMin;
+        }
+        const int64_t t0 = half ? ts + step : ts;
+        const int64_t t1 = t0 + step < te ? t0 + step : te;
+
         for (int i = tid; i < kNB; i += kPartThreads) { hist[i] = 0; nhist[i] = 0; }
         if (tid == 0) misc[0] = 0;
+
+        /* one straight-line group of coalesced 16-byte loads that the
+         * hardware writes straight into LDS (lane l of a wave to the wave's
+         * base + 16 l): no registers, each word read once, at most the one
+         * word that follows a vector read with it (a tile starts on a word:
+         * its first row is a multiple of 64). The value words start on an
+         * even word. */
+        const uint32_t trows = (uint32_t)(t1 - t0);
+        const uint32_t nkw = (trows * kwd + 63) >> 6;
+        const uint32_t nvw = (trows * vwd + 63) >> 6;
+        const uint32_t nkwp = (nkw + 1) & ~1u;
+        {
+            typedef const uint64_t __attribute__((address_space(1))) gword;
+            typedef __attribute__((address_space(3))) char lchar;
+            gword* kg = (gword*)(kwords + (((uint64_t)t0 * kwd) >> 6));
+            gword* vg = (gword*)(vwords + (((uint64_t)t0 * vwd) >> 6));
+            const uint32_t npairs = (nkwp + nvw + 1) >> 1;
+            const uint32_t wave0 = (uint32_t)__builtin_amdgcn_readfirstlane(tid & ~63);
+            constexpr int NS = (int)(kPartScratchBytes / 16) / kPartThreads;
+            #pragma unroll
+            for (int k = 0; k < NS; k++) {
+                const uint32_t p0 = k * kPartThreads + wave0;   /* the wave's first pair */
+                const uint32_t wi = 2 * (p0 + (tid & 63));
+                if (wi < 2 * npairs)
+                    __builtin_amdgcn_global_load_lds(wi < nkwp ? kg + wi : vg + (wi - nkwp),
+                                                     (lchar*)smem + 16 * p0, 16, 0, 0);
+            }
+            __builtin_amdgcn_s_waitcnt(0x0F70);   /* vmcnt(0): this wave's words are in LDS */
+        }
         __syncthreads();
 
-        /* decode once: no atomics in this loop, so the unrolled rows' loads
-         * issue together. A row past the tile or segment end re-reads the
-         * last row and is marked invalid (with the small tile of packed
-         * records that is half of a thread's rows: small inputs only).
+        /* decode once, from the staged words. A row past the tile or segment
+         * end re-reads the last row and is marked invalid (with the small
+         * tile of packed records that is half of a thread's rows: small
+         * inputs only). The filter column keeps the per-value global loads.
          * Side rows keep the decoded value in rx. */
         uint64_t rx[R];
         uint64_t ry[PACKED ? 1 : R];
         unsigned rb[R];
         #pragma unroll
         for (int i = 0; i < R; i++) {
-            const int64_t j = t0 + (int64_t)i * kPartThreads + tid;
-            const int64_t jj = j < t1 ? j : t1 - 1;
-            bool keep = j < t1;
+            const uint32_t jt = (uint32_t)(i * kPartThreads + tid);
+            const uint32_t jr = jt < trows ? jt : trows - 1;
+            const int64_t jj = t0 + jr;
+            bool keep = jt < trows;
             if (has_filter) {
                 int64_t f = zz_dec(fmin + bp_gl(fwords, fmask, fwd, jj));
                 keep = keep && f >= pp.filter_lo && f <= pp.filter_hi;
                 if (fbm) keep = keep && !bm_get(fbm, jj);
             }
-            const uint64_t kzz = kmin + bp_gl(kwords, kmask, kwd, jj);
+            const uint64_t kzz = kmin + bp_lds(scratch8, nkw, kmask, kwd, jr);
             const bool key_null = kbm && bm_get(kbm, jj);
             uint64_t vzz = 0;
             bool val_null = true;
             if (has_val) {
-                vzz = vmin + bp_gl(vwords, vmask, vwd, jj);
+                vzz = vmin + bp_lds(scratch8 + nkwp, nvw, vmask, vwd, jr);
                 val_null = vbm && bm_get(vbm, jj);
             }
             const uint64_t key = (uint64_t)zz_dec(kzz);
@@ -2246,86 +2309,158 @@ k_scan_partition(PartParams pp, const DevSeg* segs, const SegEx* segex,
             rx[i] = x;
             if constexpr (!PACKED) ry[i] = y;
         }
-        /* rank each row in its bucket; side rows (null key, INT64_MIN key)
-         * update their slots here and drop out */
-        #pragma unroll
-        for (int i = 0; i < R; i++) {
-            const unsigned c = rb[i];
-            if (c == kRowInvalid) continue;
-            if (c & kRowSide) {
-                const int side = c & 1;
-                th->side_used[side] = 1;
-                atomicAdd((unsigned long long*)&th->side_cnt[side], 1ULL);
-                if (pp.sum_slot >= 0 && !(c & 2)) {
-                    atomicAdd((unsigned long long*)&th->side_agg[side][2 * pp.sum_slot], rx[i]);
-                    atomicAdd((unsigned long long*)&th->side_agg[side][2 * pp.sum_slot + 1], 1ULL);
+        /* side rows (null key, INT64_MIN key) update their slots in a pass
+         * of their own and drop out; almost no wave has one */
+        {
+            bool side = false;
+            #pragma unroll
+            for (int i = 0; i < R; i++)
+                side = side || (rb[i] != kRowInvalid && (rb[i] & kRowSide));
+            if (__any(side)) {
+                #pragma unroll
+                for (int i = 0; i < R; i++) {
+                    const unsigned c = rb[i];
+                    if (c == kRowInvalid || !(c & kRowSide)) continue;
+                    const int sd = c & 1;
+                    th->side_used[sd] = 1;
+                    atomicAdd((unsigned long long*)&th->side_cnt[sd], 1ULL);
+                    if (pp.sum_slot >= 0 && !(c & 2)) {
+                        atomicAdd((unsigned long long*)&th->side_agg[sd][2 * pp.sum_slot], rx[i]);
+                        atomicAdd((unsigned long long*)&th->side_agg[sd][2 * pp.sum_slot + 1], 1ULL);
+                    }
+                    rb[i] = kRowInvalid;
                 }
-                rb[i] = kRowInvalid;
-                continue;
             }
-            const unsigned b = c & (kNB - 1);
-            const unsigned rank = atomicAdd((c & kRowNullVal) ? &nhist[b] : &hist[b], 1u);
-            rb[i] = c | (rank << 10);
+        }
+        /* rank each row in its bucket. No branch: a row that is out adds 0
+         * to a word of its thread's own, so the returning LDS adds issue
+         * back to back and their results are taken in a second loop */
+        {
+            unsigned rk[R];
+            #pragma unroll
+            for (int i = 0; i < R; i++) {
+                const unsigned c = rb[i];
+                const bool in = c != kRowInvalid;
+                unsigned* h = ((c & kRowNullVal) ? nhist : hist) + (c & (kNB - 1));
+                rk[i] = atomicAdd(in ? h : &hist[tid], in ? 1u : 0u);
+            }
+            #pragma unroll
+            for (int i = 0; i < R; i++)
+                if (rb[i] != kRowInvalid) rb[i] |= rk[i] << 10;
         }
         __syncthreads();
 
-        /* exclusive block scan of hist -> off[] (two consecutive buckets per
-         * thread, wave scan + wave sums), and one reservation per non-empty
-         * bucket in this workgroup's (bucket, sub) region */
+        /* exclusive block scan of hist -> off[] (two buckets per thread,
+         * wave scan + wave sums), and one reservation per non-empty
+         * bucket in this workgroup's (sub, bucket) cursor. The reservations
+         * are issued here and their bases taken after the scratch fill,
+         * which needs off[] alone. */
+        constexpr int BPT = kNB / kPartThreads;   /* thread t: buckets t and t + 512 */
+        static_assert(BPT == 2 && kPartTileMax < (1 << 16), "two 16-bit scan fields");
+        unsigned cnt[BPT], ncnt[BPT], boff[BPT];
+        unsigned long long mbase[BPT], nbase[BPT];
         {
+            /* both halves are scanned at once, as two 16-bit fields of one
+             * word: a tile's rows never carry out of the low field */
             const int lane = tid & 63, wave = tid >> 6;
-            constexpr int BPT = kNB / kPartThreads;   /* consecutive buckets per thread */
-            const int b0 = tid * BPT;
-            unsigned cnt[BPT];
-            unsigned local = 0;
-            #pragma unroll
-            for (int h = 0; h < BPT; h++) { cnt[h] = hist[b0 + h]; local += cnt[h]; }
+            cnt[0] = hist[tid];
+            cnt[1] = hist[tid + kPartThreads];
+            const unsigned local = cnt[0] | (cnt[1] << 16);
             unsigned pre = local;
             for (int sh = 1; sh < 64; sh <<= 1) {
                 unsigned o = (unsigned)__shfl_up((int)pre, sh, 64);
                 if (lane >= sh) pre += o;
             }
-            if (lane == 63) misc[2 + wave] = pre;
+            {
+                unsigned wv = wave;   /* its LDS address is formed here, as co below */
+                asm volatile("" : "+v"(wv));
+                if (lane == 63) misc[2 + wv] = pre;
+            }
             __syncthreads();
-            unsigned off = pre - local;
-            for (int w2 = 0; w2 < wave; w2++) off += misc[2 + w2];
-            if (tid == kPartThreads - 1) misc[1] = off + local;
+            unsigned excl = pre - local, all = 0;
             #pragma unroll
-            for (int h = 0; h < BPT; off += cnt[h], h++) {
-                const int b = b0 + h;
-                const unsigned c = cnt[h];
-                if (c) {
-                    unsigned long long base = atomicAdd(&cursors[b * 8 + sub], (unsigned long long)c);
-                    if ((int64_t)(base + c) > pp.bucket_stride) { th->overflow = 1; misc[0] = 1; base = 0; }
-                    delta[b] = (unsigned)base - off;
-                }
+            for (int w2 = 0; w2 < kPartThreads / 64; w2++) {
+                const unsigned ws = misc[2 + w2];
+                all += ws;
+                if (w2 < wave) excl += ws;
+            }
+            if (tid == 0) misc[1] = (all & 0xFFFFu) + (all >> 16);
+            #pragma unroll
+            for (int h = 0; h < BPT; h++) {
+                /* the cursor and histogram addresses are formed here, per
+                 * tile: kept across the tile loop they cost a dozen registers
+                 * and spill */
+                unsigned b = tid + h * kPartThreads;
+                asm volatile("" : "+v"(b));
+                const unsigned co = (unsigned)(sub * kNB) + b;
+                const unsigned off = h ? (all & 0xFFFFu) + (excl >> 16) : (excl & 0xFFFFu);
+                boff[h] = off;
+                mbase[h] = 0;
+                if (cnt[h])
+                    mbase[h] = atomicAdd(&cursors[co], (unsigned long long)cnt[h]);
                 hist[b] = off;
-                const unsigned nc = nhist[b];
-                if (nc) {
-                    unsigned long long base = atomicAdd(&ncursors[b * 8 + sub], (unsigned long long)nc);
-                    if ((int64_t)(base + nc) > pp.nbucket_stride) { th->overflow = 1; misc[0] = 1; base = 0; }
-                    nhist[b] = (unsigned)base;
+                ncnt[h] = 0;
+                nbase[h] = 0;
+                if (pp.has_val_nulls) {
+                    ncnt[h] = nhist[b];
+                    if (ncnt[h])
+                        nbase[h] = atomicAdd(&ncursors[co], (unsigned long long)ncnt[h]);
                 }
             }
         }
         __syncthreads();
 
-        if (misc[0] != 1) {   /* LDS flag: uniform across the block */
+        /* the scratch fill runs while the reservations are in flight; a tile
+         * whose guard trips below has filled its scratch for nothing */
+        {
+            /* off[] of eight rows' buckets are read together */
             #pragma unroll
-            for (int i = 0; i < R; i++) {
-                const unsigned c = rb[i];
-                if (c == kRowInvalid) continue;
-                const unsigned b = c & (kNB - 1);
-                const unsigned rank = (c >> 10) & 0x3FFFu;
-                if (c & kRowNullVal) {
-                    nrecs[((int64_t)b * 8 + sub) * pp.nbucket_stride + nhist[b] + rank] = rx[i];
-                } else if constexpr (PACKED) {
-                    scratch8[hist[b] + rank] = rx[i];
-                } else {
-                    scratch16[hist[b] + rank] = make_ulonglong2(rx[i], ry[i]);
+            for (int i0 = 0; i0 < R; i0 += 8) {
+                unsigned ro[8];
+                #pragma unroll
+                for (int i = 0; i < 8; i++) ro[i] = hist[rb[i0 + i] & (kNB - 1)];
+                #pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    const unsigned c = rb[i0 + i];
+                    if (c == kRowInvalid || (c & kRowNullVal)) continue;
+                    const unsigned at = ro[i] + ((c >> 10) & 0x3FFFu);
+                    if constexpr (PACKED) {
+                        scratch8[at] = rx[i0 + i];
+                    } else {
+                        scratch16[at] = make_ulonglong2(rx[i0 + i], ry[i0 + i]);
+                    }
                 }
             }
-            __syncthreads();
+        }
+        /* the returned bases: delta[], the null stream's bases, the guard */
+        #pragma unroll
+        for (int h = 0; h < BPT; h++) {
+            unsigned b = tid + h * kPartThreads;
+            asm volatile("" : "+v"(b));
+            if (cnt[h]) {
+                unsigned long long base = mbase[h];
+                if ((int64_t)(base + cnt[h]) > pp.bucket_stride) { th->overflow = 1; misc[0] = 1; base = 0; }
+                delta[b] = (unsigned)base - boff[h];
+            }
+            if (ncnt[h]) {
+                unsigned long long base = nbase[h];
+                if ((int64_t)(base + ncnt[h]) > pp.nbucket_stride) { th->overflow = 1; misc[0] = 1; base = 0; }
+                nhist[b] = (unsigned)base;
+            }
+        }
+        __syncthreads();
+
+        if (misc[0] != 1) {   /* LDS flag: uniform across the block */
+            if (pp.has_val_nulls) {
+                #pragma unroll
+                for (int i = 0; i < R; i++) {
+                    const unsigned c = rb[i];
+                    if (c == kRowInvalid || !(c & kRowNullVal)) continue;
+                    const unsigned b = c & (kNB - 1);
+                    const unsigned rank = (c >> 10) & 0x3FFFu;
+                    nrecs[((int64_t)b * 8 + sub) * pp.nbucket_stride + nhist[b] + rank] = rx[i];
+                }
+            }
             const unsigned total = misc[1];
             for (unsigned r = tid; r < total; r += kPartThreads) {
                 if constexpr (PACKED) {
@@ -2345,6 +2480,8 @@ k_scan_partition(PartParams pp, const DevSeg* segs, const SegEx* segex,
             }
         }
         __syncthreads();
+        if (t1 < te) half = 1;
+        else { half = 0; tile += gridDim.x; }
     }
 }
 
@@ -2386,7 +2523,7 @@ k_bucket_agg(const ulonglong2* recs, const unsigned long long* cursors,
     const uint64_t kmask = (bits_k >= 64) ? ~0ULL : ((1ULL << bits_k) - 1);
     bool full = false;
     for (int sub = 0; sub < nsub && !full; sub++) {
-    int64_t n = (int64_t)cursors[(int64_t)bucket * nsub + sub];
+    int64_t n = (int64_t)cursors[(int64_t)sub * kNB + bucket];
     const ulonglong2* rows = recs + ((int64_t)bucket * nsub + sub) * bucket_stride;
     const uint64_t* rows8 = (const uint64_t*)recs + ((int64_t)bucket * nsub + sub) * bucket_stride;
     /* 4 records per thread per pass: independent probes overlap LDS latency */
@@ -2461,7 +2598,7 @@ k_bucket_agg(const ulonglong2* recs, const unsigned long long* cursors,
     #undef LOADKV
     if (nrecs) {
         for (int sub = 0; sub < 8 && !full; sub++) {
-        int64_t nn = (int64_t)ncursors[bucket * 8 + sub];
+        int64_t nn = (int64_t)ncursors[sub * kNB + bucket];
         const uint64_t* nrows = nrecs + ((int64_t)bucket * 8 + sub) * nbucket_stride;
         for (int64_t i = tid; i < nn && !full; i += 256) {
             uint64_t key = nrows[i];
@@ -2559,7 +2696,7 @@ k_bucket_agg_direct(const ulonglong2* recs, const unsigned long long* cursors,
     const bool has_sum = sum_slot >= 0;
 
     for (int sub = 0; sub < nsub; sub++) {
-        int64_t n = (int64_t)cursors[(int64_t)bucket * nsub + sub];
+        int64_t n = (int64_t)cursors[(int64_t)sub * kNB + bucket];
         const ulonglong2* rows = recs + ((int64_t)bucket * nsub + sub) * bucket_stride;
         const uint64_t* rows8 = (const uint64_t*)recs + ((int64_t)bucket * nsub + sub) * bucket_stride;
         int64_t i = tid;
@@ -2619,7 +2756,7 @@ k_bucket_agg_direct(const ulonglong2* recs, const unsigned long long* cursors,
     }
     if (nrecs) {
         for (int sub = 0; sub < 8; sub++) {
-            int64_t nn = (int64_t)ncursors[bucket * 8 + sub];
+            int64_t nn = (int64_t)ncursors[sub * kNB + bucket];
             const uint64_t* nrows = nrecs + ((int64_t)bucket * 8 + sub) * nbucket_stride;
             for (int64_t i = tid; i < nn; i += 256) {
                 uint64_t key = nrows[i];
