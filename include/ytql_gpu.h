@@ -563,6 +563,12 @@ uint32_t yt_gpu_debug_last_scan_path(void);
  * around them. */
 int32_t yt_gpu_debug_partition_tile_rows(int large);
 
+/* Diagnostic only: 8-byte packed records of one (bucket, sub) region that
+ * one full workgroup pass of the direct-span second phase covers (the rest
+ * of a region goes in shorter turns); a full pass of the hash second phase
+ * covers half as many records. A compile-time constant of the library. */
+int32_t yt_gpu_debug_bucket_pass_records(void);
+
 /* Diagnostic only: dictionary entries (runs / rows for the direct layouts)
  * on which the calling thread's last query evaluated string predicates,
  * summed over its predicates; 0 when it had none. */

@@ -308,10 +308,21 @@ struct FastParams {
  * can run in LDS). A workgroup gathers a tile's records bucket-major in an
  * LDS scratch and copies each bucket's run out as contiguous stores.
  * Phase B (k_bucket_agg / k_bucket_agg_direct): one workgroup per bucket
- * aggregates its records in an LDS table and emits compacted OutGroups. */
+ * aggregates its records in an LDS table and emits compacted OutGroups or
+ * SlimGroups. Both flush through bucket_flush: ranks by ballot and popcount,
+ * ONE reservation per workgroup on out_counter and th->ngroups, groups
+ * stored at base + rank in slot order. The direct kernel's table is
+ * 1 << dshift slots of {cnt | nonnull << 32, sum}, an array each, and the
+ * flush's scan words behind them (64 KiB + 64 B at dshift 12: the launcher
+ * raises the kernel's dynamic LDS limit). */
 constexpr int kNB = 1024;          /* partition buckets */
 constexpr int kHSlots = 2048;      /* LDS table slots per bucket (48 KB -> 3 WGs/CU) */
 constexpr uint64_t kEmptyKey = 0x8000000000000000ULL;  /* INT64_MIN bits */
+/* k_bucket_agg_direct: a full pass of a workgroup over a sub-region of
+ * packed records is eight 16-byte loads per lane, two records each; what is
+ * left below a full pass goes in turns of one load per lane. k_bucket_agg's
+ * full pass is eight records per lane, half as many. */
+constexpr int kBucketPassRecords = 256 * 8 * 2;
 
 /* phase-A geometry: a thread holds up to 16 rows of a tile (8 with 16-byte
  * records), a compile-time constant so the tile's records and (bucket, rank)

@@ -1388,6 +1388,11 @@ extern "C" int32_t yt_gpu_debug_partition_tile_rows(int large)
     return large ? kPartTileMax : kPartTileMin;
 }
 
+extern "C" int32_t yt_gpu_debug_bucket_pass_records(void)
+{
+    return kBucketPassRecords;
+}
+
 static uint64_t next_pow2(uint64_t x)
 {
     uint64_t p = 1;

@@ -2487,6 +2487,107 @@ k_scan_partition(PartParams pp, const DevSeg* segs, const SegEx* segex,
 
 
 
+/* Phase B's flush, one for both kernels: the workgroup counts its non-empty
+ * slots (ballot + popcount per wave, wave sums in LDS), ONE thread reserves
+ * the whole run with one add on out_counter and one on th->ngroups, and
+ * every lane stores its group at base + rank. Wave w owns the w-th quarter
+ * of the 64-slot chunks, so ranks follow slot order and a bucket's groups
+ * leave as contiguous stores of adjacent lanes. A workgroup without a group
+ * issues no add. The group-limit mark is set iff a ticket of the run reaches
+ * group_limit (base + n > group_limit); a group whose index reaches out_cap
+ * sets overflow = 1 and is not written.
+ * Slots: occupied(i), and read(i, key, cnt, nonnull, sum) for an occupied
+ * slot. scanw: kFlushScanWords words of LDS that nothing else uses from the
+ * barrier before the flush on. Called by all 256 threads. */
+constexpr int kFlushScanWords = 8;      /* 4 wave counts, the base, 3 spare */
+/* the direct kernel's largest request: two 8-byte words per slot at dshift
+ * 12 (a key span of 22 bits) and the scan words */
+constexpr size_t kBucketDirectLdsMax =
+    ((size_t)16 << 12) + kFlushScanWords * sizeof(unsigned long long);
+
+template <class Slots>
+__device__ __forceinline__ void bucket_flush(const Slots sl, int nslots,
+        unsigned long long* scanw, OutGroup* out, unsigned long long* out_counter,
+        int64_t out_cap, int slim, TableHdr* th, int sum_slot, int agg_count)
+{
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int nchunks = (nslots + 63) >> 6;
+    const int cpw = (nchunks + 3) >> 2;
+    const int c0 = wave * cpw;
+    const int c1 = c0 + cpw < nchunks ? c0 + cpw : nchunks;
+
+    unsigned mine = 0;
+    for (int c = c0; c < c1; c++) {
+        const int i = c * 64 + lane;
+        mine += __popcll(__ballot(i < nslots && sl.occupied(i)));
+    }
+    if (lane == 0) scanw[wave] = mine;
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned long long n = scanw[0] + scanw[1] + scanw[2] + scanw[3];
+        unsigned long long idx = 0;
+        if (n) {
+            idx = atomicAdd(out_counter, n);
+            const unsigned long long t = atomicAdd(&th->ngroups, n);
+            if (th->group_limit > 0 && (int64_t)(t + n) > th->group_limit)
+                mark_group_limit(th);
+        }
+        scanw[4] = idx;
+    }
+    __syncthreads();
+    unsigned long long at = scanw[4];
+    for (int w = 0; w < wave; w++) at += scanw[w];
+    for (int c = c0; c < c1; c++) {
+        const int i = c * 64 + lane;
+        const bool occ = i < nslots && sl.occupied(i);
+        const unsigned long long b = __ballot(occ);
+        const unsigned long long idx = at + __popcll(b & ((1ULL << lane) - 1));
+        at += __popcll(b);
+        if (!occ) continue;
+        if ((int64_t)idx >= out_cap) { th->overflow = 1; continue; }
+        uint64_t key, cnt, nonnull, sum;
+        sl.read(i, key, cnt, nonnull, sum);
+        if (slim) {
+            ulonglong2* g2 = (ulonglong2*)((SlimGroup*)out + idx);
+            g2[0] = make_ulonglong2(key, cnt);
+            g2[1] = sum_slot >= 0 ? make_ulonglong2(sum, nonnull)
+                                  : make_ulonglong2(0, 0);
+            continue;
+        }
+        OutGroup& g = out[idx];
+        g.key_bits = key;
+        g.key_meta = 0;
+        g.cnt = cnt;
+        for (int a = 0; a < agg_count; a++) {
+            g.agg_bits[a] = 0;
+            g.agg_nonnull[a] = 0;
+        }
+        if (sum_slot >= 0) {
+            g.agg_bits[sum_slot] = sum;
+            g.agg_nonnull[sum_slot] = nonnull;
+        }
+    }
+}
+
+/* the hash kernel's table: {key, cnt | nonnull << 32, sum} */
+struct HashSlots {
+    const unsigned long long* tab;
+    __device__ __forceinline__ bool occupied(int i) const
+    {
+        return tab[i * 3] != (unsigned long long)kEmptyKey;
+    }
+    __device__ __forceinline__ void read(int i, uint64_t& key, uint64_t& cnt,
+                                         uint64_t& nonnull, uint64_t& sum) const
+    {
+        key = tab[i * 3];
+        const uint64_t cn = tab[i * 3 + 1];
+        cnt = cn & 0xFFFFFFFFULL;
+        nonnull = cn >> 32;
+        sum = tab[i * 3 + 2];
+    }
+};
+
 /* Phase B: one workgroup per bucket. LDS table slot = {key, cnt|nonnull<<32
  * packed, sum}; per-workgroup counts stay < 2^32 because a bucket's rows do.
  * Emits compacted OutGroups directly (buckets are key-disjoint), or
@@ -2502,6 +2603,7 @@ k_bucket_agg(const ulonglong2* recs, const unsigned long long* cursors,
              int nsub)
 {
     __shared__ unsigned long long tab[kHSlots * 3];
+    __shared__ unsigned long long scanw[kFlushScanWords];
     const int tid = threadIdx.x;
     const int bucket = blockIdx.x;
 
@@ -2624,41 +2726,32 @@ k_bucket_agg(const ulonglong2* recs, const unsigned long long* cursors,
     __syncthreads();
 
     /* flush compacted groups */
-    for (int i = tid; i < kHSlots; i += 256) {
-        unsigned long long key = tab[i * 3];
-        if (key == (unsigned long long)kEmptyKey) continue;
-        unsigned long long idx = atomicAdd(out_counter, 1ULL);
-        unsigned long long t = atomicAdd(&th->ngroups, 1ULL);
-        if (th->group_limit > 0 && (int64_t)t >= th->group_limit) mark_group_limit(th);
-        if ((int64_t)idx >= out_cap) { th->overflow = 1; continue; }
-        if (slim) {
-            const uint64_t cn = tab[i * 3 + 1];
-            ulonglong2* g2 = (ulonglong2*)((SlimGroup*)out + idx);
-            g2[0] = make_ulonglong2(key, cn & 0xFFFFFFFFULL);
-            g2[1] = sum_slot >= 0 ? make_ulonglong2(tab[i * 3 + 2], cn >> 32)
-                                  : make_ulonglong2(0, 0);
-            continue;
-        }
-        OutGroup& g = out[idx];
-        g.key_bits = key;
-        g.key_meta = 0;
-        uint64_t cntnn = tab[i * 3 + 1];
-        g.cnt = cntnn & 0xFFFFFFFFULL;
-        for (int a = 0; a < agg_count; a++) {
-            g.agg_bits[a] = 0;
-            g.agg_nonnull[a] = 0;
-        }
-        if (sum_slot >= 0) {
-            g.agg_bits[sum_slot] = tab[i * 3 + 2];
-            g.agg_nonnull[sum_slot] = cntnn >> 32;
-        }
-    }
+    bucket_flush(HashSlots{tab}, kHSlots, scanw, out, out_counter, out_cap,
+                 slim, th, sum_slot, agg_count);
 }
 
 
+/* the direct kernel's table: cnt | nonnull << 32 and sum in an array each;
+ * the slot index IS the key (zz-relative to key0) */
+struct DirectSlots {
+    const unsigned long long* cntnn;
+    const unsigned long long* sums;
+    uint64_t key0;
+    __device__ __forceinline__ bool occupied(int i) const { return cntnn[i] != 0; }
+    __device__ __forceinline__ void read(int i, uint64_t& key, uint64_t& cnt,
+                                         uint64_t& nonnull, uint64_t& sum) const
+    {
+        key = (uint64_t)zz_dec(key0 + (uint64_t)i);
+        cnt = cntnn[i] & 0xFFFFFFFFULL;
+        nonnull = cntnn[i] >> 32;
+        sum = sums[i];
+    }
+};
+
 /* Phase B, direct-span mode: buckets are key-RANGE slices, so the LDS
  * "table" is a dense array indexed by (krel - bucket<<dshift) — no hash,
- * no probe loop, no CAS, no stored keys. Slot = {cnt|nonnull<<32, sum}.
+ * no probe loop, no CAS, no stored keys. Slot = {cnt|nonnull<<32, sum}; the
+ * flush's scan words lie behind the two arrays.
  * Semantics identical to k_bucket_agg (registry.cpp:1783-1834 insert +
  * udf/sum.c null-propagating sum); only the table organisation differs. */
 __global__ void __launch_bounds__(256)
@@ -2681,7 +2774,7 @@ k_bucket_agg_direct(const ulonglong2* recs, const unsigned long long* cursors,
     /* a capacity guard tripped in phase A: its cursors then count records
      * that were never written and run past their regions, and the host
      * discards this pass anyway — read nothing. The flag goes through
-     * cntnn[0] (the launch sizes the LDS for the table alone). */
+     * cntnn[0], which the zeroing below takes back. */
     if (tid == 0) cntnn[0] = (th->overflow == 1);
     __syncthreads();
     const bool skip = cntnn[0] != 0;
@@ -2769,34 +2862,9 @@ k_bucket_agg_direct(const ulonglong2* recs, const unsigned long long* cursors,
     __syncthreads();
 
     /* flush: slot index IS the key (zz-relative) */
-    for (int i = tid; i < SL; i += 256) {
-        uint64_t cn = cntnn[i];
-        if (!cn) continue;
-        unsigned long long idx = atomicAdd(out_counter, 1ULL);
-        unsigned long long t = atomicAdd(&th->ngroups, 1ULL);
-        if (th->group_limit > 0 && (int64_t)t >= th->group_limit) mark_group_limit(th);
-        if ((int64_t)idx >= out_cap) { th->overflow = 1; continue; }
-        if (slim) {
-            ulonglong2* g2 = (ulonglong2*)((SlimGroup*)out + idx);
-            g2[0] = make_ulonglong2((uint64_t)zz_dec(gmin_k + base_rel + (uint64_t)i),
-                                    cn & 0xFFFFFFFFULL);
-            g2[1] = sum_slot >= 0 ? make_ulonglong2(sums[i], cn >> 32)
-                                  : make_ulonglong2(0, 0);
-            continue;
-        }
-        OutGroup& g = out[idx];
-        g.key_bits = (uint64_t)zz_dec(gmin_k + base_rel + (uint64_t)i);
-        g.key_meta = 0;
-        g.cnt = cn & 0xFFFFFFFFULL;
-        for (int a = 0; a < agg_count; a++) {
-            g.agg_bits[a] = 0;
-            g.agg_nonnull[a] = 0;
-        }
-        if (sum_slot >= 0) {
-            g.agg_bits[sum_slot] = sums[i];
-            g.agg_nonnull[sum_slot] = cn >> 32;
-        }
-    }
+    bucket_flush(DirectSlots{cntnn, sums, gmin_k + base_rel}, SL,
+                 (unsigned long long*)smem + 2 * SL, out, out_counter, out_cap,
+                 slim, th, sum_slot, agg_count);
 }
 
 
@@ -4336,7 +4404,22 @@ hipError_t ytql_launch_bucket_agg_direct(const void* recs, const unsigned long l
                                          uint64_t gmin_k, uint64_t gmin_v,
                                          int dshift, int nsub, hipStream_t st)
 {
-    size_t lds = (size_t)2 * sizeof(unsigned long long) << dshift;
+    /* the table and the flush's scan words: at dshift 12 that is 64 KiB + 64
+     * bytes, above what a launch may request by default, so raise the
+     * kernel's limit first, once per device */
+    static std::atomic<bool> raised[64];
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (dev < 0 || dev >= 64 || !raised[dev].load(std::memory_order_acquire)) {
+        e = hipFuncSetAttribute((const void*)k_bucket_agg_direct,
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)kBucketDirectLdsMax);
+        if (e != hipSuccess) return e;
+        if (dev >= 0 && dev < 64) raised[dev].store(true, std::memory_order_release);
+    }
+    size_t lds = ((size_t)16 << dshift) + kFlushScanWords * sizeof(unsigned long long);
+    if (lds > kBucketDirectLdsMax) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_bucket_agg_direct, dim3(kNB), dim3(256), lds, st,
                        (const ulonglong2*)recs, cursors, bucket_stride,
                        nrecs, ncursors, nbucket_stride,
