@@ -557,6 +557,20 @@ enum {
 };
 uint32_t yt_gpu_debug_last_scan_path(void);
 
+/* Diagnostic only: how the k-selection of the calling thread's last query
+ * (scan + ORDER BY ... LIMIT) ended. 0 after any other query, and after one
+ * that returned before its first histogram pass. */
+enum {
+    YT_TOPK_FAST        = 1 << 0,  /* the fast histogram / gather kernels ran */
+    YT_TOPK_ONLY_NULLS  = 1 << 1,  /* offset + limit took null keys only */
+    YT_TOPK_ALL_NONNULL = 1 << 2,  /* every non-null key is a candidate */
+    YT_TOPK_BIG_TIE     = 1 << 3,  /* refinement ended on one key value that
+                                      more than 2^17 rows hold */
+    YT_TOPK_PASSES_SHIFT = 8,      /* bits 8..15: histogram passes */
+    YT_TOPK_PASSES_MASK  = 0xFF << 8,
+};
+uint32_t yt_gpu_debug_last_topk(void);
+
 /* Diagnostic only: rows per tile of the partitioned GROUP BY's first phase;
  * large != 0: the tile of 8-byte packed records once a record region holds
  * that many. Compile-time constants of the library; tests size their inputs

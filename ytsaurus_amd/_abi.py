@@ -69,6 +69,14 @@ SCAN_PATH_STR_DENSE = 1 << 9
 SCAN_PATH_STR_GENERAL = 1 << 10
 SCAN_PATH_PROJ_COMPACT = 1 << 11
 
+# yt_gpu_debug_last_topk bits (diagnostic)
+TOPK_FAST = 1 << 0
+TOPK_ONLY_NULLS = 1 << 1
+TOPK_ALL_NONNULL = 1 << 2
+TOPK_BIG_TIE = 1 << 3
+TOPK_PASSES_SHIFT = 8
+TOPK_PASSES_MASK = 0xFF << 8
+
 
 class YtValueData(C.Union):
     _fields_ = [("i64", C.c_int64), ("u64", C.c_uint64),
@@ -254,6 +262,7 @@ def gpu_lib():
              [C.POINTER(YtPlan), C.POINTER(YtChunk), C.POINTER(YtExecOptions),
               C.POINTER(YtRowset), C.POINTER(YtStatistics), C.c_char_p, C.c_size_t])
         _sig(lib, "yt_gpu_debug_last_scan_path", C.c_uint32, [])
+        _sig(lib, "yt_gpu_debug_last_topk", C.c_uint32, [])
         _sig(lib, "yt_gpu_debug_partition_tile_rows", C.c_int32, [C.c_int])
         _sig(lib, "yt_gpu_debug_bucket_pass_records", C.c_int32, [])
         _sig(lib, "yt_gpu_debug_last_strpred_entries", C.c_uint64, [])

@@ -29,6 +29,7 @@ __all__ = [
     "gpu_key_ranges", "gpu_partial_mk", "gpu_merge_mk",
     "oracle_partial_str", "oracle_merge_str", "gpu_partial_str", "gpu_merge_str",
     "gpu_available", "gpu_execute", "gpu_partial", "gpu_merge",
+    "gpu_debug_last_topk",
     "rows_from_rowset", "sort_rows", "make_rowset", "coordinate_results",
 ]
 
@@ -1167,6 +1168,18 @@ def gpu_execute(plan, device_chunk, max_groups_hint=0, group_row_limit=0,
     if raw_rowset:
         return rs, st
     return rows_from_rowset(rs), st
+
+
+def gpu_debug_last_topk():
+    """TEST ONLY: yt_gpu_debug_last_topk of this thread's last query, taken
+    apart: dict of fast / only_nulls / all_nonnull / big_tie (bools) and
+    passes (histogram passes)."""
+    v = int(_abi.gpu_lib().yt_gpu_debug_last_topk())
+    return {"fast": bool(v & _abi.TOPK_FAST),
+            "only_nulls": bool(v & _abi.TOPK_ONLY_NULLS),
+            "all_nonnull": bool(v & _abi.TOPK_ALL_NONNULL),
+            "big_tie": bool(v & _abi.TOPK_BIG_TIE),
+            "passes": (v & _abi.TOPK_PASSES_MASK) >> _abi.TOPK_PASSES_SHIFT}
 
 
 def make_rowset(capacity, ncols, pool_bytes=0):

@@ -435,6 +435,7 @@ struct TopkGather {
     int32_t all_nonnull;      /* 1 = every non-null row is a strict hit */
     int32_t pad_;
     uint64_t lo, hi;          /* strict: m < lo; tie: lo <= m <= hi */
+    int64_t cap_strict;       /* rows the histograms counted below lo */
     int64_t cap_tie;
     int64_t cap_null;
 };

@@ -1383,6 +1383,15 @@ extern "C" uint32_t yt_gpu_debug_last_scan_path(void)
     return t_last_scan_path;
 }
 
+/* diagnostic: YT_TOPK_* bits of this thread's last query; only run_scan_topk
+ * writes it */
+static thread_local uint32_t t_last_topk = 0;
+
+extern "C" uint32_t yt_gpu_debug_last_topk(void)
+{
+    return t_last_topk;
+}
+
 extern "C" int32_t yt_gpu_debug_partition_tile_rows(int large)
 {
     return large ? kPartTileMax : kPartTileMin;
@@ -3012,7 +3021,16 @@ static int run_scan_topk(const YtPlan* plan, const YtChunk* chunk,
         tp.level0 = 0;
     }
 
-    if (!all_nonnull && !only_nulls && T > CAPB && plan->order_count > 1) {
+    /* refinement stops above CAPB only on one key value (shift == 0 bins are
+     * single values, lo >= hi is one) */
+    const bool big_tie = !all_nonnull && !only_nulls && T > CAPB;
+    t_last_topk = (fast_col >= 0 ? YT_TOPK_FAST : 0)
+        | (only_nulls ? YT_TOPK_ONLY_NULLS : 0)
+        | (all_nonnull ? YT_TOPK_ALL_NONNULL : 0)
+        | (big_tie ? YT_TOPK_BIG_TIE : 0)
+        | ((uint32_t)(launches > 255 ? 255 : launches) << YT_TOPK_PASSES_SHIFT);
+
+    if (big_tie && plan->order_count > 1) {
         set_err(errbuf, errlen,
                 "order-key tie set too large for multi-key ORDER BY this round");
         return YT_ERR_UNSUPPORTED;
@@ -3038,17 +3056,23 @@ static int run_scan_topk(const YtPlan* plan, const YtChunk* chunk,
     tg.all_nonnull = all_nonnull ? 1 : 0;
     tg.pad_ = 0;
     /* only_nulls: nothing strict (strict is m < lo, so lo = 0 matches
-     * no row — a mapped key CAN be 0, e.g. INT64_MIN ascending, and the
-     * strict buffer is unbounded) and at most the capped tie bucket */
+     * no row — a mapped key CAN be 0, e.g. INT64_MIN ascending, and S is
+     * 0 here) and at most the capped tie bucket */
     tg.lo = only_nulls ? 0 : lo;
     tg.hi = only_nulls ? 0 : hi;
-    tg.cap_tie = CAPB;
+    /* the ties still owed are k_nonnull - S; above CAPB that is one key
+     * value (big_tie), and with a single order key any k_nonnull - S of its
+     * rows are a correct answer (more keys were refused above) */
+    int64_t cap_tie = CAPB;
+    if (big_tie && k_nonnull - S > cap_tie) cap_tie = k_nonnull - S;
+    tg.cap_strict = S;
+    tg.cap_tie = cap_tie;
     tg.cap_null = CAPN;
     int64_t* d_rows_strict = nullptr;
     int64_t* d_rows_tie = nullptr;
     int64_t* d_rows_null = nullptr;
     HIP_CHECK(ps.dev(&d_rows_strict, sizeof(int64_t) * (S ? S : 1)));
-    HIP_CHECK(ps.dev(&d_rows_tie, sizeof(int64_t) * CAPB));
+    HIP_CHECK(ps.dev(&d_rows_tie, sizeof(int64_t) * cap_tie));
     HIP_CHECK(ps.dev(&d_rows_null, sizeof(int64_t) * CAPN));
     HIP_CHECK(hipMemsetAsync(d_ctrs, 0, 3 * sizeof(unsigned long long),
                              R2.stream));
@@ -3072,7 +3096,11 @@ static int run_scan_topk(const YtPlan* plan, const YtChunk* chunk,
     HIP_CHECK(hipMemcpy(hctrs, d_ctrs, 3 * sizeof(unsigned long long),
                         hipMemcpyDeviceToHost));
     int64_t nS = (int64_t)hctrs[0];
-    int64_t nB = (int64_t)hctrs[1] < CAPB ? (int64_t)hctrs[1] : CAPB;
+    if (nS != S) {   /* cannot happen: the gather counts what the passes did */
+        set_err(errbuf, errlen, "ORDER BY selection internal error");
+        return YT_ERR_HIP;
+    }
+    int64_t nB = (int64_t)hctrs[1] < cap_tie ? (int64_t)hctrs[1] : cap_tie;
     int64_t nN = (int64_t)hctrs[2] < CAPN ? (int64_t)hctrs[2] : CAPN;
     int64_t M = nS + nB + nN;
 
@@ -4691,6 +4719,7 @@ extern "C" int yt_gpu_query_execute(
     output->totals_row = 0;
     t_last_strpred_entries = 0;
     t_last_inlist_mode = 0;
+    t_last_topk = 0;
     if (plan->having && expr_has_strlit(plan->having)) {
         set_err(errbuf, errlen, "HAVING over string values: not this round");
         return YT_ERR_UNSUPPORTED;
@@ -4983,6 +5012,7 @@ static int query_partial_impl(
     double tw0 = now_ms();
     t_last_strpred_entries = 0;
     t_last_inlist_mode = 0;
+    t_last_topk = 0;
     DevPlan dp;
     StrPreds SP;
     rc = build_devplan(plan, chunk, &dp, &SP, errbuf, errlen);
@@ -5181,6 +5211,7 @@ extern "C" int yt_gpu_query_partial_str(
     if (stats) memset(stats, 0, sizeof(*stats));
     t_last_strpred_entries = 0;
     t_last_inlist_mode = 0;
+    t_last_topk = 0;
     StrPartialOut po;
     po.partition_count = partition_count;
     po.states_device = (YtStateRow*)states_device;

@@ -1776,7 +1776,7 @@ k_topk_gather(DevPlan p, const DevSeg* segs, const SegEx* segex,
         if (!topk_map(v, tg.desc, &m, error_out)) continue;
         if (tg.all_nonnull || m < tg.lo) {
             unsigned long long j = atomicAdd(ctr_strict, 1ULL);
-            rows_strict[j] = r;
+            if ((int64_t)j < tg.cap_strict) rows_strict[j] = r;
         } else if (m <= tg.hi) {
             unsigned long long j = atomicAdd(ctr_tie, 1ULL);
             if ((int64_t)j < tg.cap_tie) rows_tie[j] = r;
@@ -1881,7 +1881,7 @@ k_topk_gather_fast(const DevSeg* segs, const SegEx* segex, int seg_off,
             uint64_t m = topk_map_int(raw, is_signed, tg.desc);
             if (tg.all_nonnull || m < tg.lo) {
                 unsigned long long q = atomicAdd(ctr_strict, 1ULL);
-                rows_strict[q] = r;
+                if ((int64_t)q < tg.cap_strict) rows_strict[q] = r;
             } else if (m <= tg.hi) {
                 unsigned long long q = atomicAdd(ctr_tie, 1ULL);
                 if ((int64_t)q < tg.cap_tie) rows_tie[q] = r;
