@@ -289,7 +289,15 @@ typedef struct YtPlan {
      * the codegen eq-comparer treats null == null). This round: one join,
      * UNIQUE foreign keys (the dimension-lookup case; duplicate keys fail
      * loudly — the reference's cross-product expansion is round-3 work),
-     * int64/uint64/boolean key columns. The foreign value columns appear to
+     * int64/uint64/boolean key columns, or STRING key columns on both sides
+     * (compared on length and bytes; the empty string is a key and is not
+     * null). A string primary key is a column of the primary chunk; one
+     * STRING and one numeric key column is YT_ERR_INVALID_PLAN; foreign
+     * chunks of a string-key item hold fewer than 2^31 rows. String join
+     * items run with grouped plans over numeric keys, plain scans and ORDER
+     * BY ... LIMIT over numeric columns; string group keys, string
+     * predicates and string projections beside a join, and STRING foreign
+     * VALUE columns, are refused. The foreign value columns appear to
      * the rest of the plan as columns [P .. P+foreign_value_count) where P =
      * the primary chunk's column count — filter/keys/aggs/order may
      * reference them; the join applies BEFORE the WHERE clause, as in the
@@ -594,6 +602,14 @@ uint64_t yt_gpu_debug_last_strpred_entries(void);
  * probed in global memory. */
 int32_t yt_gpu_debug_last_inlist_mode(void);
 
+/* Diagnostic only: the string-key join items of the calling thread's last
+ * query. *inserted = foreign rows that claimed a slot of a string table
+ * (non-null keys); *entries = dictionary entries (runs / rows for the direct
+ * layouts) of the primary key columns' kept segments that were probed — the
+ * table is probed once per entry, not once per row. Both 0 when the query had
+ * no string-key join; either pointer may be NULL. */
+void yt_gpu_debug_last_strjoin(uint64_t* inserted, uint64_t* entries);
+
 /* Diagnostic only: blocks of the library's device/pinned buffer pool that
  * are taken and not yet given back, over all threads. A finished call holds
  * none, except what it handed out (a yt_gpu_versioned_scan_chunk handle until
@@ -787,6 +803,23 @@ int yt_inlist_eval_str(const char* list_bytes, const int64_t* list_ends,
                        const uint8_t* list_nulls, int64_t n,
                        const char* text_bytes, const int64_t* text_ends,
                        const uint8_t* text_nulls, int64_t m, uint8_t* out);
+
+/* The foreign table of a STRING-key join, exposed for format tests: built on
+ * the CPU by the rules of the GPU build (one slot per non-null row, the
+ * canonical slot holds the match list, null keys chain off the null row) and
+ * probed with the slot probe the kernels share. Needs no GPU. Foreign key i
+ * is f_bytes[f_ends[i-1] .. f_ends[i]) (f_ends[-1] = 0), null when
+ * f_nulls[i]; the probe texts likewise. out_head_row[i] = a foreign row with
+ * text i's key (null joins null), or -1; out_chain_next[r] = the next foreign
+ * row with row r's key, or -1: head and links enumerate the matches.
+ * hash_bits (1..64): build and probe keep that many low bits of the byte
+ * hash. A query always keeps 64; a test passes fewer to make equal hashes
+ * over different bytes common. */
+int yt_strjoin_eval(const char* f_bytes, const int64_t* f_ends,
+                    const uint8_t* f_nulls, int64_t n,
+                    const char* p_bytes, const int64_t* p_ends,
+                    const uint8_t* p_nulls, int64_t m, int hash_bits,
+                    int64_t* out_head_row, int64_t* out_chain_next);
 
 #ifdef __cplusplus
 } /* extern "C" */

@@ -276,6 +276,12 @@ def gpu_lib():
         _sig(lib, "yt_inlist_eval_str", C.c_int,
              [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64,
               C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
+        _sig(lib, "yt_gpu_debug_last_strjoin", None,
+             [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
+        _sig(lib, "yt_strjoin_eval", C.c_int,
+             [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64,
+              C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+              C.c_void_p, C.c_void_p])
         _sig(lib, "yt_gpu_query_partial", C.c_int,
              [C.POINTER(YtPlan), C.POINTER(YtChunk), C.POINTER(YtExecOptions),
               C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),

@@ -29,7 +29,7 @@ __all__ = [
     "gpu_key_ranges", "gpu_partial_mk", "gpu_merge_mk",
     "oracle_partial_str", "oracle_merge_str", "gpu_partial_str", "gpu_merge_str",
     "gpu_available", "gpu_execute", "gpu_partial", "gpu_merge",
-    "gpu_debug_last_topk",
+    "gpu_debug_last_topk", "gpu_debug_last_strjoin", "strjoin_eval",
     "rows_from_rowset", "sort_rows", "make_rowset", "coordinate_results",
 ]
 
@@ -1180,6 +1180,40 @@ def gpu_debug_last_topk():
             "all_nonnull": bool(v & _abi.TOPK_ALL_NONNULL),
             "big_tie": bool(v & _abi.TOPK_BIG_TIE),
             "passes": (v & _abi.TOPK_PASSES_MASK) >> _abi.TOPK_PASSES_SHIFT}
+
+
+def gpu_debug_last_strjoin():
+    """TEST ONLY: yt_gpu_debug_last_strjoin of this thread's last query:
+    (foreign rows inserted into string tables, primary entries probed)."""
+    ins, ent = C.c_uint64(0), C.c_uint64(0)
+    _abi.gpu_lib().yt_gpu_debug_last_strjoin(C.byref(ins), C.byref(ent))
+    return int(ins.value), int(ent.value)
+
+
+def _pack_strings(strings):
+    """list of bytes-or-None -> (bytes, ends int64 array, nulls uint8 array)"""
+    ends = np.cumsum([0 if s is None else len(s) for s in strings],
+                     dtype=np.int64)
+    nulls = np.array([s is None for s in strings], dtype=np.uint8)
+    return b"".join(s for s in strings if s is not None), ends, nulls
+
+
+def strjoin_eval(foreign, probes, hash_bits=64):
+    """TEST ONLY: yt_strjoin_eval — the string-key join's foreign table built
+    and probed on the CPU. foreign, probes: lists of bytes or None (null).
+    Returns (head, nxt): head[i] = a foreign row with probe i's key or -1,
+    nxt[r] = the next foreign row with row r's key or -1."""
+    fb, fe, fn = _pack_strings(foreign)
+    pb, pe, pn = _pack_strings(probes)
+    head = np.full(len(probes), -7, dtype=np.int64)
+    nxt = np.full(len(foreign), -7, dtype=np.int64)
+    rc = _abi.gpu_lib().yt_strjoin_eval(
+        fb, fe.ctypes.data, fn.ctypes.data, len(foreign),
+        pb, pe.ctypes.data, pn.ctypes.data, len(probes), int(hash_bits),
+        head.ctypes.data, nxt.ctypes.data)
+    if rc != YT_OK:
+        raise RuntimeError("yt_strjoin_eval: error %d" % rc)
+    return head.tolist(), nxt.tolist()
 
 
 def make_rowset(capacity, ncols, pool_bytes=0):

@@ -27,6 +27,7 @@ def build_gpu(force=False):
     hdrs = [os.path.join(HERE, "csrc", "common.h"),
             os.path.join(HERE, "csrc", "strpred.h"),
             os.path.join(HERE, "csrc", "inlist.h"),
+            os.path.join(HERE, "csrc", "strjoin.h"),
             os.path.join(HERE, "csrc", "launch.h"),
             os.path.join(REPO, "include", "ytql_gpu.h")]
     out = os.path.join(HERE, "libytql_gpu.so")

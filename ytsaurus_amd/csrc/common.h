@@ -140,8 +140,8 @@ struct DevPlan {
     uint64_t in_empty[kMaxInSets];
 };
 
-/* Equi-join device context (one join item, UNIQUE foreign keys — see
- * include/ytql_gpu.h YtJoin). The hash table is open-addressing with the
+/* Equi-join device context (one join item — see include/ytql_gpu.h
+ * YtJoin). The hash table is open-addressing with the
  * row index as the claim word (hrow -1 = empty); duplicate keys are
  * detected by a post-build verify kernel, so inserts never read other
  * slots' keys (no publish race). Probes run in later kernels only. */
@@ -171,7 +171,14 @@ struct JoinDev {
     const int64_t* chead;         /* [nslots] chain head row, -1 */
     const int64_t* fnext;         /* [frows] next same-key row, -1 */
     int32_t has_dups;             /* any key (incl. null) with >1 row */
-    int32_t pad2_;
+    /* 0: int64/uint64/boolean keys, hkey = the key's bits, rows probe the
+     * table. 1: STRING keys (strjoin.h), hkey = the byte hash; the table is
+     * probed once per ENTRY of the primary key column's kept segments
+     * (k_strjoin_entries) and a row reads jmap[jbase[seg] + id - 1]: the
+     * head of its key's match list, or -1. */
+    int32_t key_kind;
+    const int32_t* jmap;
+    const int64_t* jbase;         /* per kept key segment: first jmap index */
 };
 
 /* versioned scan-format read: per-segment device

@@ -24,6 +24,7 @@
 #include "common.h"
 #include "strpred.h"
 #include "inlist.h"
+#include "strjoin.h"
 #include "launch.h"
 #include "../../include/ytql_gpu.h"
 
@@ -407,6 +408,8 @@ struct StrPreds {
 };
 
 static thread_local uint64_t t_last_strpred_entries = 0;
+static thread_local uint64_t t_last_strjoin_inserted = 0;
+static thread_local uint64_t t_last_strjoin_entries = 0;
 static thread_local int32_t t_last_inlist_mode = 0;
 
 extern "C" uint64_t yt_gpu_debug_last_strpred_entries(void)
@@ -579,6 +582,78 @@ extern "C" int yt_inlist_eval_str(const char* list_bytes, const int64_t* list_en
             : (uint8_t)inlist_probe_str(il.slots.data(), il.mask, il.bytes.data(),
                                         inlist_str_hash(text_bytes + b, tn),
                                         text_bytes + b, tn);
+    }
+    return YT_OK;
+}
+
+/* strjoin_probe_slot's view of a slot's owner row, over packed host strings */
+struct HostOwnerBytes {
+    const char* bytes;
+    const int64_t* ends;
+    const char* operator()(int64_t row, uint32_t* len) const
+    {
+        const int64_t b = row ? ends[row - 1] : 0;
+        *len = (uint32_t)(ends[row] - b);
+        return bytes + b;
+    }
+};
+
+extern "C" int yt_strjoin_eval(const char* f_bytes, const int64_t* f_ends,
+                               const uint8_t* f_nulls, int64_t n,
+                               const char* p_bytes, const int64_t* p_ends,
+                               const uint8_t* p_nulls, int64_t m, int hash_bits,
+                               int64_t* out_head_row, int64_t* out_chain_next)
+{
+    if (n < 0 || m < 0 || hash_bits < 1 || hash_bits > 64 ||
+        (n && (!f_ends || !out_chain_next)) || (m && (!p_ends || !out_head_row)))
+        return YT_ERR_INVALID_PLAN;
+    const uint64_t hmask = hash_bits >= 64 ? ~0ULL : ((1ULL << hash_bits) - 1);
+    /* setup_join_item's table: load <= 0.5, at least 2048 slots */
+    uint64_t cap = 2048;
+    while (cap < (uint64_t)(n ? n : 1) * 2) cap <<= 1;
+    const uint64_t mask = cap - 1;
+    std::vector<uint64_t> hkey(cap, 0);
+    std::vector<int64_t> hrow(cap, -1), chead(cap, -1);
+    const HostOwnerBytes owner{f_bytes, f_ends};
+    int64_t null_row = -1;
+    /* k_strjoin_build: every non-null row claims the first free slot from
+     * its hash; null rows chain off null_row */
+    for (int64_t r = 0; r < n; r++) {
+        out_chain_next[r] = -1;
+        if (f_nulls && f_nulls[r]) {
+            out_chain_next[r] = null_row;
+            null_row = r;
+            continue;
+        }
+        uint32_t len = 0;
+        const char* t = owner(r, &len);
+        const uint64_t hash = inlist_str_hash(t, len) & hmask;
+        uint64_t h = hash & mask;
+        while (hrow[h] >= 0) h = (h + 1) & mask;
+        hrow[h] = r;
+        hkey[h] = hash;
+    }
+    /* k_strjoin_chain: push every row on its key's canonical slot */
+    for (int64_t r = 0; r < n; r++) {
+        if (f_nulls && f_nulls[r]) continue;
+        uint32_t len = 0;
+        const char* t = owner(r, &len);
+        const int64_t h = strjoin_probe_slot(hkey.data(), hrow.data(), mask,
+                                             inlist_str_hash(t, len) & hmask,
+                                             t, len, owner);
+        if (h < 0) return YT_ERR_INVALID_CHUNK;   /* unreachable */
+        out_chain_next[r] = chead[h];
+        chead[h] = r;
+    }
+    /* k_strjoin_entries + join_resolve: one probe per text, null joins null */
+    for (int64_t i = 0; i < m; i++) {
+        if (p_nulls && p_nulls[i]) { out_head_row[i] = null_row; continue; }
+        const int64_t b = i ? p_ends[i - 1] : 0;
+        const uint32_t tn = (uint32_t)(p_ends[i] - b);
+        const int64_t h = strjoin_probe_slot(hkey.data(), hrow.data(), mask,
+                                             inlist_str_hash(p_bytes + b, tn) & hmask,
+                                             p_bytes + b, tn, owner);
+        out_head_row[i] = h < 0 ? -1 : chead[h];
     }
     return YT_OK;
 }
@@ -2535,7 +2610,7 @@ struct JoinRun {
  * (row_types/row_ncols — primary columns plus earlier items' values, so a
  * later item can key on an earlier item's output). */
 static int setup_join_item(const YtJoin* J, const uint8_t* row_types,
-                           int row_ncols, JoinRun* JR,
+                           int row_ncols, int primary_ncols, JoinRun* JR,
                            hipStream_t stream, char* errbuf, size_t errlen)
 {
     int rc = YT_OK;
@@ -2548,10 +2623,30 @@ static int setup_join_item(const YtJoin* J, const uint8_t* row_types,
     auto intish = [](int vt) {
         return vt == YT_VT_INT64 || vt == YT_VT_UINT64 || vt == YT_VT_BOOLEAN;
     };
-    if (!intish(row_types[J->primary_key_col]) ||
-        !intish(fc->columns[J->foreign_key_col].value_type)) {
+    const int pvt = row_types[J->primary_key_col];
+    const int fvt = fc->columns[J->foreign_key_col].value_type;
+    const bool str_key = pvt == YT_VT_STRING && fvt == YT_VT_STRING;
+    if ((pvt == YT_VT_STRING) != (fvt == YT_VT_STRING)) {
+        set_err(errbuf, errlen, "join: key type mismatch");
+        return YT_ERR_INVALID_PLAN;
+    }
+    if (!str_key && (!intish(pvt) || !intish(fvt))) {
         set_err(errbuf, errlen,
                 "join: int64/uint64/boolean key columns this round");
+        return YT_ERR_UNSUPPORTED;
+    }
+    /* a string key is looked up through the entries of a primary segment
+     * (setup_strjoin_maps). An earlier item's appended value has none; string
+     * foreign values are refused below, so no plan gets this far today, but
+     * this is the bound that keeps the jmap lookup off foreign columns. */
+    if (str_key && J->primary_key_col >= primary_ncols) {
+        set_err(errbuf, errlen,
+                "join: a string key must be a column of the primary chunk");
+        return YT_ERR_UNSUPPORTED;
+    }
+    if (str_key && fc->row_count >= ((int64_t)1 << 31)) {
+        set_err(errbuf, errlen,
+                "join: string keys take foreign chunks below 2^31 rows");
         return YT_ERR_UNSUPPORTED;
     }
     for (int j = 0; j < J->foreign_value_count; j++) {
@@ -2580,13 +2675,13 @@ static int setup_join_item(const YtJoin* J, const uint8_t* row_types,
     unsigned kerr = 0;
     HIP_CHECK(JR->Rf.ps.dev(&JR->d_hkey, sizeof(uint64_t) * cap));
     HIP_CHECK(JR->Rf.ps.dev(&JR->d_hrow, sizeof(long long) * cap));
-    HIP_CHECK(JR->Rf.ps.dev(&JR->d_misc, sizeof(unsigned long long) * 2));
+    HIP_CHECK(JR->Rf.ps.dev(&JR->d_misc, sizeof(unsigned long long) * 3));
     HIP_CHECK(JR->Rf.ps.dev(&JR->d_chead, sizeof(long long) * cap));
     HIP_CHECK(JR->Rf.ps.dev(&JR->d_fnext, sizeof(long long) * (fn ? fn : 1)));
     HIP_CHECK(hipMemsetAsync(JR->d_hrow, 0xFF, sizeof(long long) * cap, stream));
     HIP_CHECK(hipMemsetAsync(JR->d_chead, 0xFF, sizeof(long long) * cap, stream));
     HIP_CHECK(hipMemsetAsync(JR->d_fnext, 0xFF, sizeof(long long) * (fn ? fn : 1), stream));
-    HIP_CHECK(hipMemsetAsync(JR->d_misc, 0, sizeof(unsigned long long) * 2, stream));
+    HIP_CHECK(hipMemsetAsync(JR->d_misc, 0, sizeof(unsigned long long) * 3, stream));
 
     jd.active = 1;
     jd.is_left = J->is_left ? 1 : 0;
@@ -2610,8 +2705,51 @@ static int setup_join_item(const YtJoin* J, const uint8_t* row_types,
     jd.chead = (const int64_t*)JR->d_chead;
     jd.fnext = (const int64_t*)JR->d_fnext;
     jd.has_dups = 0;
+    jd.key_kind = str_key ? 1 : 0;
+    jd.jmap = nullptr;
+    jd.jbase = nullptr;
 
-    if (fn > 0 && JR->Rf.nsegs > 0) {
+    if (str_key && fn > 0 && JR->Rf.nsegs > 0) {
+        /* str_key_id answers "null" for a layout it does not know */
+        const int off = JR->Rf.h_off[jd.fkey_col], cnt = JR->Rf.h_cnt[jd.fkey_col];
+        std::vector<SegEx> ex(cnt);
+        HIP_CHECK(hipMemcpy(ex.data(), JR->Rf.d_segex + off, sizeof(SegEx) * cnt,
+                            hipMemcpyDeviceToHost));
+        for (int sg = 0; sg < cnt; sg++)
+            if (!(ex[sg].flags & (8 | 32 | 64))) {
+                set_err(errbuf, errlen, "join: unknown string segment layout");
+                return YT_ERR_UNSUPPORTED;
+            }
+        /* the string table (strjoin.h): same claim word, byte hashes in
+         * hkey. The chain kernel does not read null_row, so the two launches
+         * need no readback between them. */
+        const bool timing = getenv("YTQL_TIMING") != nullptr;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (timing) {
+            HIP_CHECK(JR->Rf.ps.event(&e0));
+            HIP_CHECK(JR->Rf.ps.event(&e1));
+            HIP_CHECK(hipEventRecord(e0, stream));
+        }
+        HIP_CHECK(hipMemsetAsync(JR->Rf.d_err, 0, sizeof(unsigned), stream));
+        HIP_CHECK(ytql_launch_strjoin_build(&jd, fn, JR->d_hkey, JR->d_hrow,
+                                            JR->d_misc, (unsigned*)(JR->d_misc + 1),
+                                            JR->d_misc + 2, stream));
+        HIP_CHECK(ytql_launch_strjoin_chain(&jd, fn, (unsigned*)(JR->d_misc + 1), stream));
+        if (timing) HIP_CHECK(hipEventRecord(e1, stream));
+        unsigned long long misc[3] = {0, 0, 0};
+        HIP_CHECK(hipMemcpy(misc, JR->d_misc, sizeof(misc), hipMemcpyDeviceToHost));
+        jd.null_row = misc[0] ? (int64_t)(misc[0] - 1) : -1;
+        jd.has_dups = ((unsigned*)&misc[1])[1] != 0;
+        t_last_strjoin_inserted += misc[2];
+        if (timing) {
+            float ms = 0;
+            HIP_CHECK(hipEventSynchronize(e1));
+            HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+            fprintf(stderr, "[ytql timing] string join: %lld foreign rows, %llu "
+                            "inserted, build %.3fms\n",
+                    (long long)fn, misc[2], ms);
+        }
+    } else if (fn > 0 && JR->Rf.nsegs > 0) {
         /* d_err[0] = decode error, d_err[1] = has_dups flag (two words) */
         HIP_CHECK(hipMemsetAsync(JR->Rf.d_err, 0, sizeof(unsigned), stream));
         HIP_CHECK(hipMemsetAsync(JR->d_misc + 1, 0, sizeof(unsigned long long), stream));
@@ -2636,6 +2774,77 @@ static int setup_join_item(const YtJoin* J, const uint8_t* row_types,
     return YT_OK;
 }
 
+/* diagnostic: the string-key joins of this thread's last query — foreign
+ * rows that claimed a slot of a string table, and primary entries probed by
+ * the entry pass (both summed over the join items) */
+extern "C" void yt_gpu_debug_last_strjoin(uint64_t* inserted, uint64_t* entries)
+{
+    if (inserted) *inserted = t_last_strjoin_inserted;
+    if (entries) *entries = t_last_strjoin_entries;
+}
+
+/* String-key join items, after setup_chunk of the primary: read back the key
+ * column's parsed segments (the KEPT ones — input_row_limit truncates the
+ * list), give every entry one jmap word, run the entry pass on the run's
+ * stream and hand jmap + jbase to a COPY of the item's JoinDev in store[];
+ * *jd / *jd2 are repointed at the copies. The buffers are R's. */
+static int setup_strjoin_maps(DeviceRun* R, const JoinDev** jd, const JoinDev** jd2,
+                              JoinDev store[2], char* errbuf, size_t errlen)
+{
+    const JoinDev** items[2] = {jd, jd2};
+    for (int it = 0; it < 2; it++) {
+        const JoinDev* src = *items[it];
+        if (!src || !src->active || !src->key_kind || R->nsegs == 0) continue;
+        const bool timing = getenv("YTQL_TIMING") != nullptr;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        const int off = R->h_off[src->pkey_col], cnt = R->h_cnt[src->pkey_col];
+        std::vector<SegEx> ex(cnt ? cnt : 1);
+        if (cnt)
+            HIP_CHECK(hipMemcpy(ex.data(), R->d_segex + off, sizeof(SegEx) * cnt,
+                                hipMemcpyDeviceToHost));
+        std::vector<int64_t> base(cnt + 1);
+        int64_t entries = 0;
+        for (int sg = 0; sg < cnt; sg++) {
+            if (!(ex[sg].flags & (8 | 32 | 64))) {
+                set_err(errbuf, errlen, "join: unknown string segment layout");
+                return YT_ERR_UNSUPPORTED;
+            }
+            base[sg] = entries;
+            entries += ex[sg].dict_size;
+        }
+        base[cnt] = entries;
+        int64_t* d_base = nullptr;
+        int32_t* d_map = nullptr;
+        HIP_CHECK(R->ps.dev(&d_base, sizeof(int64_t) * (cnt + 1)));
+        HIP_CHECK(R->ps.dev(&d_map, sizeof(int32_t) * (entries ? entries : 1)));
+        /* base is pageable: the copy has left it when the call returns */
+        HIP_CHECK(hipMemcpyAsync(d_base, base.data(), sizeof(int64_t) * (cnt + 1),
+                                 hipMemcpyHostToDevice, R->stream));
+        if (timing) {
+            HIP_CHECK(R->ps.event(&e0));
+            HIP_CHECK(R->ps.event(&e1));
+            HIP_CHECK(hipEventRecord(e0, R->stream));
+        }
+        if (entries)
+            HIP_CHECK(ytql_launch_strjoin_entries(R->d_segs, R->d_segex, off, cnt,
+                                                  d_base, entries, src, d_map,
+                                                  R->stream));
+        t_last_strjoin_entries += (uint64_t)entries;
+        if (timing) {
+            float ms = 0;
+            HIP_CHECK(hipEventRecord(e1, R->stream));
+            HIP_CHECK(hipEventSynchronize(e1));
+            HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+            fprintf(stderr, "[ytql timing] string join: %lld entries, entry "
+                            "pass %.3fms\n", (long long)entries, ms);
+        }
+        store[it] = *src;
+        store[it].jmap = d_map;
+        store[it].jbase = d_base;
+        *items[it] = &store[it];
+    }
+    return YT_OK;
+}
 
 /* drive the join chain (2 items max this round; duplicate foreign keys on
  * the FIRST item only — the cross-product machinery binds item 0) */
@@ -2657,7 +2866,8 @@ static int setup_join_chain(const YtPlan* plan, const YtChunk* chunk,
             set_err(errbuf, errlen, "join: more than two join items not this round");
             return YT_ERR_UNSUPPORTED;
         }
-        int rc = setup_join_item(J, rt, rn, &JR[nj], stream, errbuf, errlen);
+        int rc = setup_join_item(J, rt, rn, chunk->column_count, &JR[nj], stream,
+                                 errbuf, errlen);
         if (rc != YT_OK) return rc;
         if (nj == 1 && JR[1].jd.has_dups) {
             set_err(errbuf, errlen,
@@ -2867,6 +3077,9 @@ static int run_scan_topk(const YtPlan* plan, const YtChunk* chunk,
                      errbuf, errlen);
     if (rc) return rc;
     rc = setup_string_preds(sp, &R2, &dpl, errbuf, errlen);
+    if (rc) return rc;
+    JoinDev jstr[2];        /* + this run's string-join maps */
+    rc = setup_strjoin_maps(&R2, &jd, &jd2, jstr, errbuf, errlen);
     if (rc) return rc;
     dp = &dpl;
     if (stats) stats->decode_time_ms = now_ms() - tw0;   /* setup phase */
@@ -3515,6 +3728,9 @@ static int run_scan_project(const YtPlan* plan, const YtChunk* chunk,
                      errbuf, errlen);
     if (rc) return rc;
     rc = setup_string_preds(sp, &R2, &dpl, errbuf, errlen);
+    if (rc) return rc;
+    JoinDev jstr[2];        /* + this run's string-join maps */
+    rc = setup_strjoin_maps(&R2, &jd, &jd2, jstr, errbuf, errlen);
     if (rc) return rc;
     dp = &dpl;
     (void)in_clamped;
@@ -4718,6 +4934,8 @@ extern "C" int yt_gpu_query_execute(
     }
     output->totals_row = 0;
     t_last_strpred_entries = 0;
+    t_last_strjoin_inserted = 0;
+    t_last_strjoin_entries = 0;
     t_last_inlist_mode = 0;
     t_last_topk = 0;
     if (plan->having && expr_has_strlit(plan->having)) {
@@ -4837,6 +5055,9 @@ extern "C" int yt_gpu_query_execute(
                      options->group_row_limit, errbuf, errlen);
     if (rc) return rc;
     rc = setup_string_preds(&SP, &R, &dp, errbuf, errlen);
+    if (rc) return rc;
+    JoinDev jstr[2];
+    rc = setup_strjoin_maps(&R, &jd, &jd2, jstr, errbuf, errlen);
     if (rc) return rc;
 
     const bool timing = getenv("YTQL_TIMING") != nullptr;   /* phase breakdown to stderr */
@@ -5011,6 +5232,8 @@ static int query_partial_impl(
 
     double tw0 = now_ms();
     t_last_strpred_entries = 0;
+    t_last_strjoin_inserted = 0;
+    t_last_strjoin_entries = 0;
     t_last_inlist_mode = 0;
     t_last_topk = 0;
     DevPlan dp;
@@ -5059,6 +5282,9 @@ static int query_partial_impl(
     rc = setup_join_chain(plan, chunk, JRp, &pjd, &pjd2,
                           (hipStream_t)(uintptr_t)options->stream,
                           errbuf, errlen);
+    if (rc) return rc;
+    JoinDev jstr[2];
+    rc = setup_strjoin_maps(&R, &pjd, &pjd2, jstr, errbuf, errlen);
     if (rc) return rc;
     /* dup foreign keys on item 0 are fine here: a partial is always grouped */
     rc = run_scan(plan, chunk, options, &R, &dp, pjd, pjd2, &fs, maxw, stats,
@@ -5210,6 +5436,8 @@ extern "C" int yt_gpu_query_partial_str(
     if (!options) options = &defopt;
     if (stats) memset(stats, 0, sizeof(*stats));
     t_last_strpred_entries = 0;
+    t_last_strjoin_inserted = 0;
+    t_last_strjoin_entries = 0;
     t_last_inlist_mode = 0;
     t_last_topk = 0;
     StrPartialOut po;

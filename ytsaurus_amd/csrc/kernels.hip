@@ -26,6 +26,7 @@
 #include "common.h"
 #include "strpred.h"
 #include "inlist.h"
+#include "strjoin.h"
 #include "launch.h"
 #include "../../include/ytql_gpu.h"
 
@@ -633,6 +634,7 @@ __device__ int64_t join_resolve(const DevPlan& p, ColCtx& c);
 __device__ int64_t join_resolve2(const DevPlan& p, ColCtx& c);
 __device__ DVal jforeign_at(const JoinDev& jt, int fcol, int shift,
                             int64_t frow, uint8_t vt);
+__device__ DVal str_entry_at(const DevSeg& s, const SegEx& e, int64_t j, int seg);
 
 __device__ DVal col_value(const DevPlan& p, ColCtx& c, int col)
 {
@@ -680,6 +682,9 @@ __device__ DVal col_value(const DevPlan& p, ColCtx& c, int col)
         }
     }
     const DevSeg& s = c.segs[off + lo];
+    /* a STRING column has no 64-bit value: its entry stands for it */
+    if (s.is_signed == 2)
+        return str_entry_at(s, c.segex[off + lo], c.row - s.start_row, lo);
     return seg_value_at(s, c.segex[off + lo], c.row - s.start_row, p.col_types[col]);
 }
 
@@ -722,6 +727,11 @@ __device__ int64_t join_resolve(const DevPlan& p, ColCtx& c)
         c.jrow = jt.null_row;
         return c.jrow;
     }
+    if (jt.key_kind) {
+        /* STRING key: k is its entry (str_entry_at), probed by k_strjoin_entries */
+        c.jrow = jt.jmap[jt.jbase[k.bits >> 32] + (int64_t)(k.bits & 0xFFFFFFFFu)];
+        return c.jrow;
+    }
     uint64_t h = mix64(k.bits) & jt.hmask;
     for (;;) {
         int64_t r = jt.hrow[h];
@@ -744,6 +754,10 @@ __device__ int64_t join_resolve2(const DevPlan& p, ColCtx& c)
     DVal k = col_value(p, c, jt.pkey_col);
     if (k.null_) {
         c.jrow2 = jt.null_row;
+        return c.jrow2;
+    }
+    if (jt.key_kind) {
+        c.jrow2 = jt.jmap[jt.jbase[k.bits >> 32] + (int64_t)(k.bits & 0xFFFFFFFFu)];
         return c.jrow2;
     }
     uint64_t h = mix64(k.bits) & jt.hmask;
@@ -807,6 +821,22 @@ __device__ __noinline__ DVal str_pred_row(const DevPlan& p, const ColCtx& c, con
         const uint64_t bit = (uint64_t)p.sp_base[pi][lo] * 64 + (id - 1);
         v.bits = (p.sp_bits[pi][bit >> 6] >> (bit & 63)) & 1;
     }
+    return v;
+}
+
+/* The value col_value gives for a row of a STRING column: a reference to its
+ * entry, (index of the segment in its column) << 32 | id - 1, or null. Only
+ * a STRING-key join reads it (join_resolve: one jmap word per entry, filled by
+ * k_strjoin_entries); expressions over string columns never compile to P_COL.
+ * Out of line for the reason given at str_pred_row. */
+__device__ __noinline__ DVal str_entry_at(const DevSeg& s, const SegEx& e, int64_t j,
+                                          int seg)
+{
+    const uint64_t id = str_key_id(s, e, j);
+    DVal v;
+    v.type = YT_VT_STRING;
+    v.null_ = id == 0;
+    v.bits = id ? (((uint64_t)seg << 32) | (id - 1)) : 0;
     return v;
 }
 
@@ -3578,6 +3608,146 @@ k_inlist_str_entries(const DevSeg* segs, const SegEx* segex, int seg_off, int ns
 }
 
 /* ------------------------------------------------------------------ */
+/* STRING-key equi-join (common.h JoinDev.key_kind = 1, strjoin.h): the   */
+/* foreign table over byte hashes, and one probe per primary entry.      */
+
+/* the key of foreign row frow: its bytes, or nullptr for a null key */
+__device__ __forceinline__ const char* jforeign_str(const JoinDev& jt, int64_t frow,
+                                                    uint32_t* len)
+{
+    const int off = jt.f_off[jt.fkey_col];
+    int lo;
+    if (jt.fkey_shift) {
+        lo = (int)(frow >> jt.fkey_shift);
+    } else {
+        int hi = jt.f_cnt[jt.fkey_col];
+        lo = 0;
+        while (lo + 1 < hi) {
+            int mid = (lo + hi) / 2;
+            if (jt.fsegs[off + mid].start_row <= frow) lo = mid;
+            else hi = mid;
+        }
+    }
+    const DevSeg& s = jt.fsegs[off + lo];
+    const SegEx& e = jt.fsegex[off + lo];
+    const uint64_t id = str_key_id(s, e, frow - s.start_row);
+    if (id == 0) return nullptr;
+    return dict_entry(s, e, (int64_t)(id - 1), len);
+}
+
+/* strjoin_probe_slot's view of a slot's owner row */
+struct JForeignOwner {
+    const JoinDev& jt;
+    __device__ const char* operator()(int64_t row, uint32_t* len) const
+    {
+        return jforeign_str(jt, row, len);
+    }
+};
+
+/* k_join_build for STRING keys: a row claims a slot by CAS on hrow, walking
+ * from its byte hash, and stores the hash in hkey. Inserts never read another
+ * slot's key, so there is no publish race. The empty string is a key like any
+ * other; null keys chain off null_row. inserted += the slots claimed, one
+ * atomic per wave. */
+__global__ void __launch_bounds__(256)
+k_strjoin_build(JoinDev jt, int64_t frows, uint64_t* hkey, long long* hrow,
+                unsigned long long* null_row_plus1, unsigned* error_out,
+                unsigned long long* inserted)
+{
+    unsigned mine = 0;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         r < frows; r += stride) {
+        uint32_t len = 0;
+        const char* t = jforeign_str(jt, r, &len);
+        if (!t) {
+            unsigned long long prev = atomicExch(null_row_plus1,
+                                                 (unsigned long long)(r + 1));
+            ((int64_t*)jt.fnext)[r] = (int64_t)prev - 1;
+            if (prev != 0ULL) atomicOr(error_out + 1, 1u);   /* has_dups */
+            continue;
+        }
+        const uint64_t hash = inlist_str_hash(t, len);
+        uint64_t h = hash & jt.hmask;
+        for (;;) {
+            unsigned long long prev = atomicCAS(
+                (unsigned long long*)&hrow[h],
+                (unsigned long long)(long long)-1,
+                (unsigned long long)r);
+            if (prev == (unsigned long long)(long long)-1) {
+                hkey[h] = hash;
+                mine++;
+                break;
+            }
+            h = (h + 1) & jt.hmask;
+        }
+    }
+    for (int sh = 32; sh >= 1; sh >>= 1) mine += __shfl_xor((int)mine, sh, 64);
+    if ((threadIdx.x & 63) == 0 && mine)
+        atomicAdd(inserted, (unsigned long long)mine);
+}
+
+/* k_join_chain for STRING keys, after all inserts are visible: every row
+ * finds its key's canonical slot (strjoin_probe_slot: equal hash AND the
+ * owner's length and bytes) and pushes itself on that slot's match list. A
+ * row always finds a slot: its own lies on its probe path. */
+__global__ void __launch_bounds__(256)
+k_strjoin_chain(JoinDev jt, int64_t frows, unsigned* error_out)
+{
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         r < frows; r += stride) {
+        uint32_t len = 0;
+        const char* t = jforeign_str(jt, r, &len);
+        if (!t) continue;
+        const int64_t h = strjoin_probe_slot(jt.hkey, jt.hrow, jt.hmask,
+                                             inlist_str_hash(t, len), t, len,
+                                             JForeignOwner{jt});
+        if (h < 0) continue;                          /* unreachable */
+        int64_t prev = (int64_t)atomicExch(
+            (unsigned long long*)&((int64_t*)jt.chead)[h],
+            (unsigned long long)r);
+        ((int64_t*)jt.fnext)[r] = prev;
+        if (prev >= 0) atomicOr(error_out + 1, 1u);   /* has_dups */
+    }
+}
+
+/* String join entry pass: the shape of k_strpred_entries with a 32-bit answer
+ * per entry and not a bit. Entry id-1 of kept key segment seg owns
+ * jmap[jbase[seg] + id-1]; a lane takes one entry, hashes its bytes, probes
+ * the foreign table and stores the head of the match list (chead of the
+ * canonical slot) or -1. Consecutive lanes store consecutive words, every
+ * word of [0, jbase[nsegs]) exactly once: no memset, no atomics. Null entries
+ * of the direct layouts get the answer of whatever bytes their offsets span
+ * (none): null rows never look them up. */
+__global__ void __launch_bounds__(256)
+k_strjoin_entries(const DevSeg* segs, const SegEx* segex, int seg_off, int nsegs,
+                  const int64_t* jbase, JoinDev jt, int32_t* jmap)
+{
+    const int64_t total = jbase[nsegs];
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += stride) {
+        /* the last segment whose first entry <= i: segments without entries
+         * own no word and are stepped over */
+        int lo = 0, hi = nsegs;
+        while (lo + 1 < hi) {
+            int mid = (lo + hi) / 2;
+            if (jbase[mid] <= i) lo = mid;
+            else hi = mid;
+        }
+        const DevSeg& s = segs[seg_off + lo];
+        const SegEx& e = segex[seg_off + lo];
+        uint32_t len;
+        const char* t = dict_entry(s, e, i - jbase[lo], &len);
+        const int64_t h = strjoin_probe_slot(jt.hkey, jt.hrow, jt.hmask,
+                                             inlist_str_hash(t, len), t, len,
+                                             JForeignOwner{jt});
+        jmap[i] = h < 0 ? -1 : (int32_t)jt.chead[h];
+    }
+}
+
+/* ------------------------------------------------------------------ */
 /* scan + project with STRING projections: stable device compaction of  */
 /* one window and the byte gather (common.h ProjTot, StrGatherRec).     */
 /* k_scan_project has left out[r * np + pj] and pass[r]; a string value */
@@ -4555,6 +4725,45 @@ hipError_t ytql_launch_join_chain(const JoinDev* jd, int64_t frows,
     int grid = (int)(want > 4096 ? 4096 : (want > 0 ? want : 1));
     hipLaunchKernelGGL(k_join_chain, dim3(grid), dim3(block), 0, st,
                        *jd, frows, error_out);
+    return hipGetLastError();
+}
+
+hipError_t ytql_launch_strjoin_build(const JoinDev* jd, int64_t frows,
+                                     uint64_t* hkey, long long* hrow,
+                                     unsigned long long* null_row_plus1,
+                                     unsigned* error_out,
+                                     unsigned long long* inserted, hipStream_t st)
+{
+    int block = 256;
+    int64_t want = (frows + block - 1) / block;
+    int grid = (int)(want > 4096 ? 4096 : (want > 0 ? want : 1));
+    hipLaunchKernelGGL(k_strjoin_build, dim3(grid), dim3(block), 0, st,
+                       *jd, frows, hkey, hrow, null_row_plus1, error_out, inserted);
+    return hipGetLastError();
+}
+
+hipError_t ytql_launch_strjoin_chain(const JoinDev* jd, int64_t frows,
+                                     unsigned* error_out, hipStream_t st)
+{
+    int block = 256;
+    int64_t want = (frows + block - 1) / block;
+    int grid = (int)(want > 4096 ? 4096 : (want > 0 ? want : 1));
+    hipLaunchKernelGGL(k_strjoin_chain, dim3(grid), dim3(block), 0, st,
+                       *jd, frows, error_out);
+    return hipGetLastError();
+}
+
+/* entries = jbase[nsegs], the length of jmap */
+hipError_t ytql_launch_strjoin_entries(const DevSeg* segs, const SegEx* segex,
+                                       int seg_off, int nsegs,
+                                       const int64_t* jbase, int64_t entries,
+                                       const JoinDev* jd, int32_t* jmap,
+                                       hipStream_t st)
+{
+    int64_t want = (entries + 255) / 256;
+    int grid = (int)(want > 4096 ? 4096 : (want > 0 ? want : 1));
+    hipLaunchKernelGGL(k_strjoin_entries, dim3(grid), dim3(256), 0, st,
+                       segs, segex, seg_off, nsegs, jbase, *jd, jmap);
     return hipGetLastError();
 }
 

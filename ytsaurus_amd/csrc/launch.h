@@ -73,6 +73,14 @@ hipError_t ytql_launch_join_build(const ytql::JoinDev*, int64_t, uint64_t*,
                                   hipStream_t);
 hipError_t ytql_launch_join_chain(const ytql::JoinDev*, int64_t, unsigned*,
                                    hipStream_t);
+hipError_t ytql_launch_strjoin_build(const ytql::JoinDev*, int64_t, uint64_t*,
+                                     long long*, unsigned long long*, unsigned*,
+                                     unsigned long long*, hipStream_t);
+hipError_t ytql_launch_strjoin_chain(const ytql::JoinDev*, int64_t, unsigned*,
+                                     hipStream_t);
+hipError_t ytql_launch_strjoin_entries(const ytql::DevSeg*, const ytql::SegEx*, int, int,
+                                       const int64_t*, int64_t, const ytql::JoinDev*,
+                                       int32_t*, hipStream_t);
 hipError_t ytql_launch_scan_project(const ytql::DevPlan*, const ytql::DevSeg*, const ytql::SegEx*,
                                     const int32_t*, const int32_t*, int64_t,
                                     int64_t, const ytql::JoinDev*, const ytql::JoinDev*,
