@@ -585,6 +585,13 @@ uint32_t yt_gpu_debug_last_topk(void);
  * around them. */
 int32_t yt_gpu_debug_partition_tile_rows(int large);
 
+/* Diagnostic only: which instantiation of the first phase's kernel the
+ * process's last partitioned GROUP BY launched. 0: 16-byte records (or no
+ * launch yet); 1: 8-byte packed records; 3: packed records and the plain
+ * decode (a direct-span key of at most 32 bits per segment beside a value,
+ * no filter, no nulls, no INT64_MIN key). */
+int32_t yt_gpu_debug_partition_variant(void);
+
 /* Diagnostic only: 8-byte packed records of one (bucket, sub) region that
  * one full workgroup pass of the direct-span second phase covers (the rest
  * of a region goes in shorter turns); a full pass of the hash second phase

@@ -264,6 +264,7 @@ def gpu_lib():
         _sig(lib, "yt_gpu_debug_last_scan_path", C.c_uint32, [])
         _sig(lib, "yt_gpu_debug_last_topk", C.c_uint32, [])
         _sig(lib, "yt_gpu_debug_partition_tile_rows", C.c_int32, [C.c_int])
+        _sig(lib, "yt_gpu_debug_partition_variant", C.c_int32, [])
         _sig(lib, "yt_gpu_debug_bucket_pass_records", C.c_int32, [])
         _sig(lib, "yt_gpu_debug_last_strpred_entries", C.c_uint64, [])
         _sig(lib, "yt_gpu_debug_pool_blocks_in_use", C.c_uint64, [])

@@ -375,7 +375,21 @@ struct PartParams {
      * phase A re-derives a record's bucket the same way. */
     int32_t direct_mode;
     int32_t dshift;               /* per-bucket key-slot range = 1 << dshift */
+    /* the plain decode (kernels.hip part_decode_plain): packed_mode and
+     * direct_mode, a value column, no filter, no nulls in key or value,
+     * every key segment at most 32 bits wide and the key column's zigzag
+     * maximum below UINT64_MAX, so that no row is a side row (INT64_MIN has
+     * zz = UINT64_MAX). The widths are bounded through the segment headers'
+     * range, so a header range that saturates at UINT64_MAX rules it out
+     * too, whatever an exact scan found. The launcher picks the
+     * instantiation by it. */
+    int32_t plain_mode;
+    int32_t pad_;
 };
+
+/* which k_scan_partition a launch ran (yt_gpu_debug_partition_variant) */
+constexpr int kPartVariantPacked = 1;
+constexpr int kPartVariantPlain = 2;   /* set together with packed */
 
 /* string-keyed GROUP BY (BASELINE config 5 family): dictionary-encoded
  * string key segments aggregate by per-segment dictionary id into dense

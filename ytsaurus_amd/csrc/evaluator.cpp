@@ -1472,6 +1472,15 @@ extern "C" int32_t yt_gpu_debug_partition_tile_rows(int large)
     return large ? kPartTileMax : kPartTileMin;
 }
 
+/* diagnostic: kPartVariant* bits of the process's last phase-A launch; only
+ * run_partitioned writes it */
+static std::atomic<int32_t> g_last_part_variant{0};
+
+extern "C" int32_t yt_gpu_debug_partition_variant(void)
+{
+    return g_last_part_variant.load(std::memory_order_relaxed);
+}
+
 extern "C" int32_t yt_gpu_debug_bucket_pass_records(void)
 {
     return kBucketPassRecords;
@@ -1842,6 +1851,25 @@ static int run_partitioned(const YtPlan* plan, const YtChunk* chunk,
             pp.dshift = bk > 10 ? bk - 10 : 0;
             if (tried_direct) *tried_direct = true;
         }
+        /* the plain decode (common.h PartParams::plain_mode). The column's
+         * zigzag maximum, from the headers or exact, bounds every row: below
+         * UINT64_MAX no key is INT64_MIN. The headers' own range is
+         * min(min_value) .. max(min_value + 2^w - 1) over the key's
+         * segments, saturated at UINT64_MAX: unsaturated and narrower than
+         * 2^32 it holds every segment's width w to 32 bits. A saturated
+         * header range therefore keeps the general decode even where an
+         * exact scan found a lower maximum: the widths are unknown then.
+         * (Direct mode itself needs a header span of at most 23 bits, the
+         * widest the exact key scan runs for, so no segment wider than 23
+         * bits gets here today; the 32 is the kernel's own limit.) */
+        if (pp.packed_mode && pp.direct_mode && pp.filter_idx < 0 && pp.val_idx >= 0 &&
+            !pp.has_key_nulls && !pp.has_val_nulls && R->h_setup &&
+            R->col_zzmax[fs->key_col] != UINT64_MAX) {
+            const uint64_t hlo = R->h_setup->zzmin[fs->key_col];
+            const uint64_t hhi = R->h_setup->zzmax[fs->key_col];
+            if (hhi != UINT64_MAX && hhi >= hlo && hhi - hlo < (1ULL << 32))
+                pp.plain_mode = 1;
+        }
         if (pp.direct_mode) path |= YT_SCAN_PATH_DIRECT;
         if (pp.packed_mode) path |= YT_SCAN_PATH_PACKED;
         if (pp.has_val_nulls) path |= YT_SCAN_PATH_NULL_STREAM;
@@ -1929,6 +1957,9 @@ static int run_partitioned(const YtPlan* plan, const YtChunk* chunk,
                                          R->d_th, R->d_cursors, R->d_recs,
                                          R->d_ncursors, R->d_nrecs,
                                          grid, R->stream));
+    g_last_part_variant.store((pp.packed_mode ? kPartVariantPacked : 0) |
+                              (pp.plain_mode ? kPartVariantPlain : 0),
+                              std::memory_order_relaxed);
     HIP_CHECK(hipEventRecord(ev1, R->stream));
     if (pp.direct_mode) {
         HIP_CHECK(ytql_launch_bucket_agg_direct(R->d_recs, R->d_cursors, pp.bucket_stride,

@@ -2144,6 +2144,73 @@ constexpr unsigned kRowInvalid = 0xFFFFFFFFu;   /* masked, filtered out, or done
 constexpr unsigned kRowSide = 0x80000000u;      /* | side (bit 0) | val_null << 1 */
 constexpr unsigned kRowNullVal = 0x40000000u;   /* goes to the null-value stream */
 
+/* The plain decode of k_scan_partition: packed records, direct span, a value
+ * column, no filter, no nulls, key fields of at most 32 bits and no
+ * INT64_MIN key in the column (PartParams::plain_mode). Nothing is tested per
+ * row: rb[i] is the row's bucket, or kRowInvalid past the tile's end.
+ *   - A field is cut from a window of dwords that starts at the dword
+ *     holding its first bit: two adjacent dwords (one LDS read with two
+ *     offsets, 4-byte aligned) for a field of up to 32 bits, three for a
+ *     value of 33..64 bits (WIDE), then v_alignbit by the bit's low five
+ *     bits and one mask. The window is not clamped: its last dword may lie
+ *     one dword past the staged words. That dword is still inside the
+ *     workgroup's LDS (the key's words are followed by the value's, the
+ *     scratch by the histograms) and every bit it brings is masked away.
+ *   - The key stays in 32 bits: the tile's kmin - gmin_k is added to the raw
+ *     field (mod 2^32; the column's span is below 2^22) and the bucket is a
+ *     32-bit shift. The value gets the tile's vmin - gmin_v in 64 bits.
+ *   - A thread's row i lies 512 w bits behind its row i - 1, so positions
+ *     advance by addition; a position past the tile's last row is held at
+ *     that row, as the general decode holds the row index.
+ *   - The LDS reads of eight rows are issued before the first use. */
+template <bool WIDE, int R>
+__device__ __forceinline__ void part_decode_plain(const uint32_t* sk, const uint32_t* sv,
+        uint32_t kwd, uint32_t vwd, uint32_t trows, uint32_t kadd, uint64_t vadd,
+        unsigned bits_k, unsigned dshift, uint32_t tid,
+        uint64_t (&rx)[R], unsigned (&rb)[R])
+{
+    constexpr int G = 8;
+    static_assert(R % G == 0, "whole groups of rows");
+    const uint32_t kmask = kwd >= 32 ? ~0u : (1u << kwd) - 1;
+    const uint32_t vtop = WIDE ? vwd - 32 : vwd;   /* bits of the value's masked dword */
+    const uint32_t vmask = vtop >= 32 ? ~0u : (1u << vtop) - 1;
+    const uint32_t klast = (trows - 1) * kwd, vlast = (trows - 1) * vwd;
+    const uint32_t kstep = kPartThreads * kwd, vstep = kPartThreads * vwd;
+    uint32_t kbit = tid * kwd, vbit = tid * vwd, jt = tid;
+    #pragma unroll
+    for (int i0 = 0; i0 < R; i0 += G) {
+        uint32_t k0[G], k1[G], v0[G], v1[G], v2[WIDE ? G : 1], ks[G], vs[G];
+        #pragma unroll
+        for (int i = 0; i < G; i++) {
+            ks[i] = kbit < klast ? kbit : klast;
+            vs[i] = vbit < vlast ? vbit : vlast;
+            const uint32_t* pk = sk + (ks[i] >> 5);
+            const uint32_t* pv = sv + (vs[i] >> 5);
+            k0[i] = pk[0];
+            k1[i] = pk[1];
+            v0[i] = pv[0];
+            v1[i] = pv[1];
+            if constexpr (WIDE) v2[i] = pv[2];
+            kbit += kstep;
+            vbit += vstep;
+        }
+        /* the group's reads stay ahead of its first use: the scheduler
+         * otherwise pairs them off two rows at a time */
+        __builtin_amdgcn_sched_barrier(0);
+        #pragma unroll
+        for (int i = 0; i < G; i++) {
+            const uint32_t krel = (__builtin_amdgcn_alignbit(k1[i], k0[i], ks[i]) & kmask) + kadd;
+            uint32_t lo = __builtin_amdgcn_alignbit(v1[i], v0[i], vs[i]), hi = 0;
+            if constexpr (WIDE) hi = __builtin_amdgcn_alignbit(v2[i], v1[i], vs[i]) & vmask;
+            else lo &= vmask;
+            const uint64_t vrel = (((uint64_t)hi << 32) | lo) + vadd;
+            rx[i0 + i] = (uint64_t)krel | (vrel << bits_k);
+            rb[i0 + i] = jt < trows ? krel >> dshift : kRowInvalid;
+            jt += kPartThreads;
+        }
+    }
+}
+
 /* Phase A. Canonical column slots: 0 = filter, 1 = key, 2 = value.
  * A tile is R rows per thread, R a compile-time constant, so the decoded
  * records and their (bucket, rank) words stay in registers and every row is
@@ -2163,8 +2230,11 @@ constexpr unsigned kRowNullVal = 0x40000000u;   /* goes to the null-value stream
  *      its record's bucket and stores to base[b] + (r - off[b]), so a
  *      bucket's run leaves as contiguous stores from adjacent lanes.
  * Null-value rows (key only, rare) go straight to their own stream, from
- * registers, in step 5. */
-template <bool PACKED>
+ * registers, in step 5.
+ * PLAIN (PartParams::plain_mode) replaces step 2's decode by
+ * part_decode_plain and compiles the side pass and the null stream out;
+ * steps 3 to 5 are the same code. */
+template <bool PACKED, bool PLAIN>
 __global__ void __launch_bounds__(kPartThreads, 4)
 k_scan_partition(PartParams pp, const DevSeg* segs, const SegEx* segex,
                  const FastCol* cols, TableHdr* th,
@@ -2173,6 +2243,7 @@ k_scan_partition(PartParams pp, const DevSeg* segs, const SegEx* segex,
                  unsigned long long* ncursors,       /* 8 x kNB null-value stream */
                  uint64_t* nrecs)
 {
+    static_assert(PACKED || !PLAIN, "the plain decode writes packed records");
     constexpr int R = (PACKED ? kPartTileMax : kPartTileMin) / kPartThreads;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -2295,53 +2366,67 @@ k_scan_partition(PartParams pp, const DevSeg* segs, const SegEx* segex,
         uint64_t rx[R];
         uint64_t ry[PACKED ? 1 : R];
         unsigned rb[R];
-        #pragma unroll
-        for (int i = 0; i < R; i++) {
-            const uint32_t jt = (uint32_t)(i * kPartThreads + tid);
-            const uint32_t jr = jt < trows ? jt : trows - 1;
-            const int64_t jj = t0 + jr;
-            bool keep = jt < trows;
-            if (has_filter) {
-                int64_t f = zz_dec(fmin + bp_gl(fwords, fmask, fwd, jj));
-                keep = keep && f >= pp.filter_lo && f <= pp.filter_hi;
-                if (fbm) keep = keep && !bm_get(fbm, jj);
+        if constexpr (PLAIN) {
+            const uint32_t* sk = (const uint32_t*)smem;
+            const uint32_t* sv = sk + 2 * nkwp;
+            const uint32_t kadd = (uint32_t)(kmin - pp.gmin_k);
+            const uint64_t vadd = vmin - pp.gmin_v;
+            if (vwd > 32)   /* uniform, per tile */
+                part_decode_plain<true, R>(sk, sv, kwd, vwd, trows, kadd, vadd,
+                                           pp.bits_k, pp.dshift, tid, rx, rb);
+            else
+                part_decode_plain<false, R>(sk, sv, kwd, vwd, trows, kadd, vadd,
+                                            pp.bits_k, pp.dshift, tid, rx, rb);
+        } else {
+            #pragma unroll
+            for (int i = 0; i < R; i++) {
+                const uint32_t jt = (uint32_t)(i * kPartThreads + tid);
+                const uint32_t jr = jt < trows ? jt : trows - 1;
+                const int64_t jj = t0 + jr;
+                bool keep = jt < trows;
+                if (has_filter) {
+                    int64_t f = zz_dec(fmin + bp_gl(fwords, fmask, fwd, jj));
+                    keep = keep && f >= pp.filter_lo && f <= pp.filter_hi;
+                    if (fbm) keep = keep && !bm_get(fbm, jj);
+                }
+                const uint64_t kzz = kmin + bp_lds(scratch8, nkw, kmask, kwd, jr);
+                const bool key_null = kbm && bm_get(kbm, jj);
+                uint64_t vzz = 0;
+                bool val_null = true;
+                if (has_val) {
+                    vzz = vmin + bp_lds(scratch8 + nkwp, nvw, vmask, vwd, jr);
+                    val_null = vbm && bm_get(vbm, jj);
+                }
+                const uint64_t key = (uint64_t)zz_dec(kzz);
+                const unsigned b = pp.direct_mode
+                    ? (unsigned)((kzz - pp.gmin_k) >> pp.dshift)
+                    : (unsigned)(mix64(key) >> 40) & (kNB - 1);
+                unsigned cls;
+                uint64_t x, y = 0;
+                if (key_null || key == kEmptyKey) {
+                    cls = kRowSide | (key_null ? 1u : 0u) | (val_null ? 2u : 0u);
+                    x = (uint64_t)zz_dec(vzz);
+                } else if (has_val && val_null) {
+                    cls = kRowNullVal | b;
+                    x = key;
+                } else if constexpr (PACKED) {
+                    cls = b;
+                    x = kzz - pp.gmin_k;
+                    if (has_val) x |= (vzz - pp.gmin_v) << pp.bits_k;
+                } else {
+                    cls = b;
+                    x = key;
+                    y = has_val ? (uint64_t)zz_dec(vzz) : 0;
+                }
+                rb[i] = keep ? cls : kRowInvalid;
+                rx[i] = x;
+                if constexpr (!PACKED) ry[i] = y;
             }
-            const uint64_t kzz = kmin + bp_lds(scratch8, nkw, kmask, kwd, jr);
-            const bool key_null = kbm && bm_get(kbm, jj);
-            uint64_t vzz = 0;
-            bool val_null = true;
-            if (has_val) {
-                vzz = vmin + bp_lds(scratch8 + nkwp, nvw, vmask, vwd, jr);
-                val_null = vbm && bm_get(vbm, jj);
-            }
-            const uint64_t key = (uint64_t)zz_dec(kzz);
-            const unsigned b = pp.direct_mode
-                ? (unsigned)((kzz - pp.gmin_k) >> pp.dshift)
-                : (unsigned)(mix64(key) >> 40) & (kNB - 1);
-            unsigned cls;
-            uint64_t x, y = 0;
-            if (key_null || key == kEmptyKey) {
-                cls = kRowSide | (key_null ? 1u : 0u) | (val_null ? 2u : 0u);
-                x = (uint64_t)zz_dec(vzz);
-            } else if (has_val && val_null) {
-                cls = kRowNullVal | b;
-                x = key;
-            } else if constexpr (PACKED) {
-                cls = b;
-                x = kzz - pp.gmin_k;
-                if (has_val) x |= (vzz - pp.gmin_v) << pp.bits_k;
-            } else {
-                cls = b;
-                x = key;
-                y = has_val ? (uint64_t)zz_dec(vzz) : 0;
-            }
-            rb[i] = keep ? cls : kRowInvalid;
-            rx[i] = x;
-            if constexpr (!PACKED) ry[i] = y;
         }
         /* side rows (null key, INT64_MIN key) update their slots in a pass
-         * of their own and drop out; almost no wave has one */
-        {
+         * of their own and drop out; almost no wave has one. The plain
+         * decode has none. */
+        if constexpr (!PLAIN) {
             bool side = false;
             #pragma unroll
             for (int i = 0; i < R; i++)
@@ -2371,7 +2456,7 @@ k_scan_partition(PartParams pp, const DevSeg* segs, const SegEx* segex,
             for (int i = 0; i < R; i++) {
                 const unsigned c = rb[i];
                 const bool in = c != kRowInvalid;
-                unsigned* h = ((c & kRowNullVal) ? nhist : hist) + (c & (kNB - 1));
+                unsigned* h = ((!PLAIN && (c & kRowNullVal)) ? nhist : hist) + (c & (kNB - 1));
                 rk[i] = atomicAdd(in ? h : &hist[tid], in ? 1u : 0u);
             }
             #pragma unroll
@@ -2431,7 +2516,7 @@ k_scan_partition(PartParams pp, const DevSeg* segs, const SegEx* segex,
                 hist[b] = off;
                 ncnt[h] = 0;
                 nbase[h] = 0;
-                if (pp.has_val_nulls) {
+                if (!PLAIN && pp.has_val_nulls) {
                     ncnt[h] = nhist[b];
                     if (ncnt[h])
                         nbase[h] = atomicAdd(&ncursors[co], (unsigned long long)ncnt[h]);
@@ -2481,7 +2566,7 @@ k_scan_partition(PartParams pp, const DevSeg* segs, const SegEx* segex,
         __syncthreads();
 
         if (misc[0] != 1) {   /* LDS flag: uniform across the block */
-            if (pp.has_val_nulls) {
+            if (!PLAIN && pp.has_val_nulls) {
                 #pragma unroll
                 for (int i = 0; i < R; i++) {
                     const unsigned c = rb[i];
@@ -4520,25 +4605,31 @@ hipError_t ytql_launch_scan_partition(const PartParams* pp, const DevSeg* segs,
     /* 64 KiB record scratch + histograms: above the 64 KiB a launch may
      * request by default, so raise the kernel's limit first, once per
      * device and instantiation */
-    static std::atomic<bool> raised[2][64];
+    static std::atomic<bool> raised[3][64];
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
-    const int inst = pp->packed_mode ? 1 : 0;
+    if (pp->plain_mode && !pp->packed_mode) return hipErrorInvalidValue;
+    const int inst = pp->plain_mode ? 2 : pp->packed_mode ? 1 : 0;
     if (dev < 0 || dev >= 64 || !raised[inst][dev].load(std::memory_order_acquire)) {
-        const void* fn = inst ? (const void*)k_scan_partition<true>
-                              : (const void*)k_scan_partition<false>;
+        const void* fn = inst == 2 ? (const void*)k_scan_partition<true, true>
+                       : inst == 1 ? (const void*)k_scan_partition<true, false>
+                                   : (const void*)k_scan_partition<false, false>;
         e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)kPartLdsBytes);
         if (e != hipSuccess) return e;
         if (dev >= 0 && dev < 64) raised[inst][dev].store(true, std::memory_order_release);
     }
-    if (pp->packed_mode)
-        hipLaunchKernelGGL(k_scan_partition<true>, dim3(grid), dim3(kPartThreads),
+    if (inst == 2)
+        hipLaunchKernelGGL((k_scan_partition<true, true>), dim3(grid), dim3(kPartThreads),
+                           kPartLdsBytes, st, *pp, segs, segex, cols, th, cursors,
+                           (ulonglong2*)recs, ncursors, nrecs);
+    else if (inst == 1)
+        hipLaunchKernelGGL((k_scan_partition<true, false>), dim3(grid), dim3(kPartThreads),
                            kPartLdsBytes, st, *pp, segs, segex, cols, th, cursors,
                            (ulonglong2*)recs, ncursors, nrecs);
     else
-        hipLaunchKernelGGL(k_scan_partition<false>, dim3(grid), dim3(kPartThreads),
+        hipLaunchKernelGGL((k_scan_partition<false, false>), dim3(grid), dim3(kPartThreads),
                            kPartLdsBytes, st, *pp, segs, segex, cols, th, cursors,
                            (ulonglong2*)recs, ncursors, nrecs);
     return hipGetLastError();
