@@ -191,6 +191,37 @@ enum {
  * column of a plain scan. The CPU oracle's scan mode has no string
  * projections. */
 
+/* STRING group keys beside other keys (yt_gpu_query_execute; key_count 2..4).
+ * Every key is exactly YT_EX_COLUMN over a column of the primary chunk, of
+ * type INT64, UINT64, BOOLEAN or STRING in any mix and order; more than one
+ * STRING key and the same column twice are allowed. Strings group on length
+ * and bytes: equal bytes are one group whatever segment, dictionary, run or
+ * row they come from; null is a key of its own and the empty string is a
+ * value, not null. A STRING key comes back as YtValue{type YT_VT_STRING,
+ * length, data.str} with the bytes appended to YtRowset.string_pool
+ * (string_pool_used is reset, then grows by exactly the sum of the emitted
+ * key lengths; a pool that cannot take them is YT_ERR_CAPACITY "string pool
+ * too small"; a null or zero-capacity pool is fine when that sum is 0); a
+ * null key is YT_VT_NULL, and so is every key of the WITH TOTALS row. The
+ * plan may hold any filter the interpreter takes (string predicates and
+ * string IN on a key column or another STRING column included), 0
+ * aggregates (DISTINCT) or 1..4 of sum / sum(1) / min / max / avg / first
+ * over numeric expressions, HAVING over numeric values, WITH TOTALS, ORDER BY
+ * ... LIMIT/OFFSET on the output (STRING keys may be ORDER BY columns), and
+ * input_row_limit / output_row_limit / group_row_limit / max_groups_hint as
+ * an integer multi-key plan does. Each distinct string of a STRING key column
+ * takes one code of the packed composite key, so the column's component is
+ * the smallest width that holds 0..D (D distinct strings in the kept
+ * segments) and the refusal of a composite wider than 62 bits applies to the
+ * sum of all widths.
+ * Refused with YT_ERR_UNSUPPORTED: a STRING key beside a join,
+ * post-projections on a plan with a STRING key, HAVING that reads a string
+ * value, a STRING column inside a key expression or an aggregate argument,
+ * a key column of 2^30 entries or more, and yt_gpu_key_ranges /
+ * yt_gpu_query_partial_mk / yt_gpu_merge_states_mk with a STRING key (the
+ * codes are local to one chunk and cannot be exchanged). One STRING key
+ * alone keeps its own path (YT_SCAN_PATH_STR_DENSE / _STR_GENERAL). */
+
 typedef struct YtExpr {
     int32_t op;           /* YT_EX_* */
     int32_t col;          /* for YT_EX_COLUMN */
@@ -562,6 +593,9 @@ enum {
                                             projection: device compaction and
                                             byte gather; 0 after any other plain
                                             scan, with or without ORDER BY */
+    /* multi-key GROUP BY with a STRING key: beside YT_SCAN_PATH_GENERIC */
+    YT_SCAN_PATH_STR_IDS     = 1 << 12, /* string ids numbered once per entry
+                                           and packed into the composite key */
 };
 uint32_t yt_gpu_debug_last_scan_path(void);
 
@@ -616,6 +650,15 @@ int32_t yt_gpu_debug_last_inlist_mode(void);
  * table is probed once per entry, not once per row. Both 0 when the query had
  * no string-key join; either pointer may be NULL. */
 void yt_gpu_debug_last_strjoin(uint64_t* inserted, uint64_t* entries);
+
+/* Diagnostic only: the string-id passes of the calling thread's last query
+ * (multi-key GROUP BY with STRING keys, below): *entries = dictionary entries
+ * (runs / rows for the direct layouts) of the STRING key columns' kept
+ * segments that the pass covered, *distinct = distinct strings numbered (D),
+ * both summed over the plan's STRING key columns (a column that is a key
+ * twice counts once). Both 0 after any other query; either pointer may be
+ * NULL. */
+void yt_gpu_debug_last_strkey(uint64_t* entries, uint64_t* distinct);
 
 /* Diagnostic only: blocks of the library's device/pinned buffer pool that
  * are taken and not yet given back, over all threads. A finished call holds

@@ -68,6 +68,7 @@ SCAN_PATH_GENERIC = 1 << 8
 SCAN_PATH_STR_DENSE = 1 << 9
 SCAN_PATH_STR_GENERAL = 1 << 10
 SCAN_PATH_PROJ_COMPACT = 1 << 11
+SCAN_PATH_STR_IDS = 1 << 12
 
 # yt_gpu_debug_last_topk bits (diagnostic)
 TOPK_FAST = 1 << 0
@@ -278,6 +279,8 @@ def gpu_lib():
              [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64,
               C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
         _sig(lib, "yt_gpu_debug_last_strjoin", None,
+             [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
+        _sig(lib, "yt_gpu_debug_last_strkey", None,
              [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
         _sig(lib, "yt_strjoin_eval", C.c_int,
              [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64,

@@ -30,6 +30,7 @@ __all__ = [
     "oracle_partial_str", "oracle_merge_str", "gpu_partial_str", "gpu_merge_str",
     "gpu_available", "gpu_execute", "gpu_partial", "gpu_merge",
     "gpu_debug_last_topk", "gpu_debug_last_strjoin", "strjoin_eval",
+    "gpu_debug_last_strkey",
     "rows_from_rowset", "sort_rows", "make_rowset", "coordinate_results",
 ]
 
@@ -1188,6 +1189,14 @@ def gpu_debug_last_strjoin():
     ins, ent = C.c_uint64(0), C.c_uint64(0)
     _abi.gpu_lib().yt_gpu_debug_last_strjoin(C.byref(ins), C.byref(ent))
     return int(ins.value), int(ent.value)
+
+
+def gpu_debug_last_strkey():
+    """TEST ONLY: yt_gpu_debug_last_strkey of this thread's last query:
+    (entries the string-id passes covered, distinct strings numbered)."""
+    ent, dis = C.c_uint64(0), C.c_uint64(0)
+    _abi.gpu_lib().yt_gpu_debug_last_strkey(C.byref(ent), C.byref(dis))
+    return int(ent.value), int(dis.value)
 
 
 def _pack_strings(strings):

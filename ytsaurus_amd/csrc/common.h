@@ -106,7 +106,8 @@ struct DevPlan {
      * zigzag-space value is biased by kp_base and offset by 1 (0 = null),
      * then packed at kp_shift. Total width <= 62 bits so the table's empty
      * (0x8000...) sentinel can never collide; key_bits == 0 (all-null key)
-     * rides the existing side-accumulator path. */
+     * rides the existing side-accumulator path. A STRING component packs
+     * its string id (StrKeyDev below). */
     int32_t kp_count;
     int32_t kp_col[kMaxPackKeys];
     int32_t kp_signed[kMaxPackKeys];
@@ -138,6 +139,18 @@ struct DevPlan {
     const uint64_t* in_tab[kMaxInSets];
     uint64_t in_mask[kMaxInSets];
     uint64_t in_empty[kMaxInSets];
+};
+
+/* STRING components of the composite key (col_types[kp_col[i]] is
+ * YT_VT_STRING): the code of a non-null value is 1 + its string id,
+ * kmap[i][kbase[i][seg] + id in seg - 1] (k_strkey_*: one id per distinct
+ * string of the column's kept segments); kp_base is 0 and kp_bits holds
+ * codes 0..D. Device pointers, filled by the host after the segment parse.
+ * An argument of k_scan_generic alone: DevPlan, which every interpreter
+ * kernel copies, stays as it was. */
+struct StrKeyDev {
+    const uint32_t* kmap[kMaxPackKeys];
+    const int64_t* kbase[kMaxPackKeys];
 };
 
 /* Equi-join device context (one join item — see include/ytql_gpu.h
@@ -437,6 +450,16 @@ struct StrSlot {
     uint64_t pad_;
 };
 static_assert(sizeof(StrSlot) == 64, "one cache line per slot");
+
+/* one distinct string of a multi-key GROUP BY's STRING key column
+ * (kernels.hip k_strkey_*), index = its dense id. Brought to the host once
+ * per query with the byte pool: D records, not one per group. */
+struct StrKeyId {
+    uint64_t off_len;             /* pool offset << 24 | length */
+    unsigned long long rep;       /* claim word of the owner entry (StrSlot) */
+};
+/* kmap word of an entry without an id (a null entry of a direct layout) */
+constexpr uint32_t kStrKeyNoId = 0xFFFFFFFFu;
 
 /* ORDER BY ... LIMIT k-selection (see kernels.hip k_topk_*).
  * Range-adaptive digits: candidates are mapped keys in [lo, hi]; digit =

@@ -315,6 +315,7 @@ static uint8_t expr_static_type(const YtExpr* e, const uint8_t* col_types)
 }
 
 static bool expr_is_col(const YtExpr* e, int* col);
+static void hexpr_cols(const YtExpr* e, uint64_t* mask);
 
 /* does the expression read a STRING column? The device interpreter decodes
  * integer, boolean and double layouts only; it would misread a string blob
@@ -410,7 +411,21 @@ struct StrPreds {
 static thread_local uint64_t t_last_strpred_entries = 0;
 static thread_local uint64_t t_last_strjoin_inserted = 0;
 static thread_local uint64_t t_last_strjoin_entries = 0;
+static thread_local uint64_t t_last_strkey_entries = 0;
+static thread_local uint64_t t_last_strkey_distinct = 0;
 static thread_local int32_t t_last_inlist_mode = 0;
+
+/* is component i of the composite key a STRING column (packs a string id)? */
+static inline bool kp_is_str(const DevPlan* dp, int i)
+{
+    return dp->col_types[dp->kp_col[i]] == YT_VT_STRING;
+}
+
+/* the distinct strings of one STRING key column on the host: id -> bytes */
+struct StrKeyTab {
+    std::vector<StrKeyId> ids;
+    std::vector<char> pool;
+};
 
 extern "C" uint64_t yt_gpu_debug_last_strpred_entries(void)
 {
@@ -940,13 +955,35 @@ static int build_devplan(const YtPlan* plan, const YtChunk* chunk, DevPlan* p,
                 return YT_ERR_UNSUPPORTED;
             }
             uint8_t vt = p->col_types[c];
-            if (vt != YT_VT_INT64 && vt != YT_VT_UINT64 && vt != YT_VT_BOOLEAN) {
+            if (vt != YT_VT_INT64 && vt != YT_VT_UINT64 && vt != YT_VT_BOOLEAN &&
+                vt != YT_VT_STRING) {
                 set_err(errbuf, errlen,
-                        "multi-key GROUP BY: int64/uint64/boolean keys this round");
+                        "multi-key GROUP BY: int64/uint64/boolean/string keys "
+                        "this round");
                 return YT_ERR_UNSUPPORTED;
             }
             p->kp_col[i] = c;
             p->kp_signed[i] = vt == YT_VT_INT64;
+            /* a STRING key packs its string id (setup_strkey_ids) */
+            if (vt != YT_VT_STRING) continue;
+            if (plan->join) {
+                set_err(errbuf, errlen,
+                        "multi-key GROUP BY: a string key beside a join: not "
+                        "this round");
+                return YT_ERR_UNSUPPORTED;
+            }
+            if (plan->project_count) {
+                set_err(errbuf, errlen,
+                        "multi-key GROUP BY: post-projections on a plan with a "
+                        "string key: not this round");
+                return YT_ERR_UNSUPPORTED;
+            }
+            uint64_t hmask = 0;
+            hexpr_cols(plan->having, &hmask);
+            if ((hmask >> i) & 1) {
+                set_err(errbuf, errlen, "HAVING over string values: not this round");
+                return YT_ERR_UNSUPPORTED;
+            }
         }
     }
     if (plan->agg_count == 0 && plan->key_count == 0) {
@@ -1405,6 +1442,8 @@ static int heval(const YtExpr* e, const HVal* row, int nrow, HVal* out)
 /* device chunk setup                                                  */
 
 struct DeviceRun {
+    /* string ids of the composite key's STRING components (setup_strkey_ids) */
+    StrKeyDev strkeys = {};
     std::vector<DevSeg> h_segs;
     std::vector<int32_t> h_off, h_cnt;
     DevSeg* d_segs = nullptr;
@@ -2049,6 +2088,8 @@ static int run_scan(const YtPlan* plan, const YtChunk* chunk,
 
     t_last_scan_path = (partitioned ? t_last_scan_path : 0)
         | (fs->valid ? YT_SCAN_PATH_FAST : YT_SCAN_PATH_GENERIC);
+    for (int i = 0; dp && i < dp->kp_count; i++)
+        if (kp_is_str(dp, i)) t_last_scan_path |= YT_SCAN_PATH_STR_IDS;
 
     rc = ensure_slots(R, plan->agg_count, errbuf, errlen);
     if (rc != YT_OK) return rc;
@@ -2129,7 +2170,7 @@ static int run_scan(const YtPlan* plan, const YtChunk* chunk,
             gen_rows = options->input_row_limit;
         HIP_CHECK(ytql_launch_scan_generic(dp, R->d_segs, R->d_segex, R->d_off, R->d_cnt,
                                            gen_rows, jd, jd2, R->d_th, R->d_slots,
-                                           R->d_err, R->stream));
+                                           R->d_err, &R->strkeys, R->stream));
         HIP_CHECK(hipEventRecord(ev1, R->stream));
     }
     HIP_CHECK(hipStreamSynchronize(R->stream));
@@ -2160,13 +2201,20 @@ static inline int64_t h_zz_dec(uint64_t z)
 /* resolve composite-key packing widths from the parsed per-column
  * zigzag-space ranges (k_parse_segments min/max atomics) */
 static int pack_group_key(DevPlan* dp, const DeviceRun* R,
-                          char* errbuf, size_t errlen)
+                          char* errbuf, size_t errlen,
+                          const StrKeyTab* strtabs = nullptr)
 {
     int shift = 0;
     for (int i = 0; i < dp->kp_count; i++) {
         int c = dp->kp_col[i];
         uint64_t lo = R->col_zzmin[c], hi = R->col_zzmax[c];
         uint64_t span = hi >= lo ? hi - lo : 0;
+        if (kp_is_str(dp, i)) {
+            /* string ids 0..D-1 (setup_strkey_ids): codes 0 (null) .. D */
+            const uint64_t D = strtabs ? strtabs[i].ids.size() : 0;
+            lo = 0;
+            span = D ? D - 1 : 0;
+        }
         /* codes are 0 (null) .. span+1: smallest bits with span+1 < 2^bits */
         int bits = 1;
         while (bits < 64 && ((span + 1) >> bits) != 0) bits++;
@@ -2263,7 +2311,8 @@ static int emit_rows(const YtPlan* plan, const YtChunk* chunk,
                      int64_t output_row_limit, int* out_limited,
                      YtRowset* output, char* errbuf, size_t errlen,
                      const SlimGroup* slim = nullptr,
-                     const SlimSlices* slices = nullptr)
+                     const SlimSlices* slices = nullptr,
+                     const StrKeyTab* strtabs = nullptr)
 {
     uint8_t col_types[kMaxCols];
     memset(col_types, YT_VT_INT64, sizeof(col_types));
@@ -2277,6 +2326,14 @@ static int emit_rows(const YtPlan* plan, const YtChunk* chunk,
     }
 
     const int kp = dp ? dp->kp_count : 0;
+    /* STRING components of the composite key: their bytes go to the rowset's
+     * string pool as rows are emitted, one row after the other */
+    bool kp_any_str = false;
+    for (int i = 0; i < kp; i++) kp_any_str |= kp_is_str(dp, i);
+    if (kp_any_str) {
+        if (!strtabs) return YT_ERR_INVALID_PLAN;
+        output->string_pool_used = 0;   /* rowsets reusable across queries */
+    }
     uint8_t key_type = YT_VT_INT64;
     int has_key = plan->key_count == 1;
     if (has_key) key_type = expr_static_type(plan->keys[0], col_types);
@@ -2293,6 +2350,7 @@ static int emit_rows(const YtPlan* plan, const YtChunk* chunk,
     auto emit_at = [&](YtValue* dst, uint64_t key_bits, int key_null,
                        uint64_t cnt, const uint64_t* ab, const uint64_t* an) -> int {
         HVal row[kMaxPackKeys + 1 + kMaxAggs];
+        uint32_t slen[kMaxPackKeys] = {0, 0, 0, 0};
         int nrow = 0;
         if (kp) {
             /* unpack the composite key (DevPlan kp_*; code 0 = null) */
@@ -2303,6 +2361,25 @@ static int emit_rows(const YtPlan* plan, const YtChunk* chunk,
                 if (code == 0) {
                     row[nrow].type = YT_VT_NULL;
                     row[nrow].bits = 0;
+                } else if (kp_is_str(dp, i)) {
+                    /* string id code-1: bits = where its bytes went */
+                    const StrKeyTab& T = strtabs[i];
+                    if (code - 1 >= T.ids.size()) return YT_ERR_HIP;
+                    const uint64_t ol = T.ids[code - 1].off_len;
+                    const uint32_t len = (uint32_t)(ol & 0xFFFFFF);
+                    if (len && (!output->string_pool ||
+                                (uint64_t)output->string_pool_used + len >
+                                    (uint64_t)output->string_pool_capacity)) {
+                        set_err(errbuf, errlen, "string pool too small");
+                        return YT_ERR_CAPACITY;
+                    }
+                    char* kdst = output->string_pool
+                        ? output->string_pool + output->string_pool_used : nullptr;
+                    if (len) memcpy(kdst, T.pool.data() + (ol >> 24), len);
+                    output->string_pool_used += len;
+                    slen[i] = len;
+                    row[nrow].type = YT_VT_STRING;
+                    row[nrow].bits = (uint64_t)(uintptr_t)kdst;
                 } else {
                     uint64_t z = code - 1 + dp->kp_base[i];
                     row[nrow].type = col_types[dp->kp_col[i]];
@@ -2334,7 +2411,7 @@ static int emit_rows(const YtPlan* plan, const YtChunk* chunk,
                 dst[i].id = (uint16_t)i;
                 dst[i].type = row[i].type;
                 dst[i].flags = 0;
-                dst[i].length = 0;
+                dst[i].length = i < kp ? slen[i] : 0;
                 dst[i].data.bits = row[i].bits;
             }
         }
@@ -2428,7 +2505,7 @@ static int emit_rows(const YtPlan* plan, const YtChunk* chunk,
     {
         const int64_t total_sides = (int64_t)(th.side_used[0] != 0)
                                   + (int64_t)(th.side_used[1] != 0);
-        const bool par_ok = ngroups >= 65536
+        const bool par_ok = ngroups >= 65536 && !kp_any_str
             && (output_row_limit <= 0 ||
                 output_row_limit >= ngroups + total_sides)
             && ngroups + total_sides <= output->capacity_rows;
@@ -2873,6 +2950,179 @@ static int setup_strjoin_maps(DeviceRun* R, const JoinDev** jd, const JoinDev** 
         store[it].jmap = d_map;
         store[it].jbase = d_base;
         *items[it] = &store[it];
+    }
+    return YT_OK;
+}
+
+/* diagnostic: the string-id passes of this thread's last query — entries
+ * covered and distinct strings found, summed over the plan's STRING key
+ * columns (a column that is a key twice is numbered once) */
+extern "C" void yt_gpu_debug_last_strkey(uint64_t* entries, uint64_t* distinct)
+{
+    if (entries) *entries = t_last_strkey_entries;
+    if (distinct) *distinct = t_last_strkey_distinct;
+}
+
+/* STRING components of a multi-key plan, after setup_chunk: number the
+ * distinct strings of each such column over the entries of its KEPT segments
+ * (the set setup_strjoin_maps walks) — hash, claim, compact, remap
+ * (kernels.hip k_strkey_*) on the run's stream — and hand kmap + kbase to the
+ * plan. The id table and its bytes come to the host once, for emit_rows.
+ * kmap and kbase are R's; the pass's scratch goes back before it returns. */
+static int setup_strkey_ids(DeviceRun* R, const DevPlan* dp,
+                            StrKeyTab tabs[kMaxPackKeys],
+                            char* errbuf, size_t errlen)
+{
+    const bool timing = getenv("YTQL_TIMING") != nullptr;
+    for (int i = 0; i < dp->kp_count; i++) {
+        if (!kp_is_str(dp, i)) continue;
+        const int col = dp->kp_col[i];
+        int same = -1;
+        for (int j = 0; j < i; j++)
+            if (dp->kp_col[j] == col) { same = j; break; }
+        if (same >= 0) {
+            R->strkeys.kmap[i] = R->strkeys.kmap[same];
+            R->strkeys.kbase[i] = R->strkeys.kbase[same];
+            tabs[i] = tabs[same];
+            continue;
+        }
+        const int off = R->h_off[col], cnt = R->h_cnt[col];
+        std::vector<SegEx> ex(cnt ? cnt : 1);
+        if (cnt)
+            HIP_CHECK(hipMemcpy(ex.data(), R->d_segex + off, sizeof(SegEx) * cnt,
+                                hipMemcpyDeviceToHost));
+        std::vector<int64_t> base(cnt + 1);
+        int64_t entries = 0;
+        uint64_t pool_cap = 0;
+        for (int sg = 0; sg < cnt; sg++) {
+            if (!(ex[sg].flags & (8 | 32 | 64))) {
+                set_err(errbuf, errlen, "string keys: unknown key segment layout");
+                return YT_ERR_UNSUPPORTED;
+            }
+            base[sg] = entries;
+            entries += ex[sg].dict_size;
+            /* a segment's blob bounds the bytes of its entries */
+            pool_cap += (uint64_t)R->h_segs[off + sg].blob_bytes;
+        }
+        base[cnt] = entries;
+        if (entries >= ((int64_t)1 << 30)) {
+            set_err(errbuf, errlen,
+                    "multi-key GROUP BY: string key column with 2^30 entries "
+                    "or more: not this round");
+            return YT_ERR_UNSUPPORTED;
+        }
+        if (pool_cap < 1024) pool_cap = 1024;
+        const size_t ne = (size_t)(entries ? entries : 1);
+
+        PoolScope ps;               /* the pass's scratch */
+        int64_t* d_base = nullptr;
+        uint32_t* d_map = nullptr;
+        uint64_t* d_hashes = nullptr;
+        uint64_t* d_idents = nullptr;
+        ulonglong2* d_pfxs = nullptr;
+        TableHdr* d_kth = nullptr;
+        StrSlot* d_slots = nullptr;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        HIP_CHECK(R->ps.dev(&d_base, sizeof(int64_t) * (cnt + 1)));
+        HIP_CHECK(R->ps.dev(&d_map, sizeof(uint32_t) * ne));
+        HIP_CHECK(ps.dev(&d_hashes, sizeof(uint64_t) * ne));
+        HIP_CHECK(ps.dev(&d_idents, sizeof(uint64_t) * ne));
+        HIP_CHECK(ps.dev(&d_pfxs, sizeof(ulonglong2) * ne));
+        HIP_CHECK(ps.dev(&d_kth, sizeof(TableHdr)));
+        /* base is pageable: the copy has left it when the call returns */
+        HIP_CHECK(hipMemcpyAsync(d_base, base.data(), sizeof(int64_t) * (cnt + 1),
+                                 hipMemcpyHostToDevice, R->stream));
+        HIP_CHECK(hipMemsetAsync(d_kth, 0, sizeof(TableHdr), R->stream));
+        if (timing) {
+            HIP_CHECK(ps.event(&e0));
+            HIP_CHECK(ps.event(&e1));
+            HIP_CHECK(hipEventRecord(e0, R->stream));
+        }
+        /* the table: as run_string_group sizes it — half the entries to
+         * start with, 4x on overflow up to twice the entries */
+        uint64_t nslots_cap = next_pow2((uint64_t)ne * 2);
+        if (nslots_cap < 2048) nslots_cap = 2048;
+        uint64_t nslots = next_pow2((uint64_t)ne / 2 + 1);
+        if (nslots < 2048) nslots = 2048;
+        if (nslots > nslots_cap) nslots = nslots_cap;
+        TableHdr kth;
+        memset(&kth, 0, sizeof(kth));
+        if (entries) {
+            HIP_CHECK(ytql_launch_strgrp_hash(R->d_segs, R->d_segex, off, cnt, d_base,
+                                              d_hashes, d_idents, d_pfxs, entries,
+                                              R->stream));
+            for (;;) {
+                HIP_CHECK(ps.dev(&d_slots, sizeof(StrSlot) * nslots));
+                HIP_CHECK(hipMemsetAsync(d_slots, 0, sizeof(StrSlot) * nslots,
+                                         R->stream));
+                HIP_CHECK(ytql_launch_strkey_claim(R->d_segs, R->d_segex, off, cnt,
+                                                   d_base, d_hashes, d_idents,
+                                                   d_pfxs, d_slots, nslots, d_map,
+                                                   d_kth, entries, R->stream));
+                HIP_CHECK(hipMemcpyAsync(&kth, d_kth, sizeof(kth),
+                                         hipMemcpyDeviceToHost, R->stream));
+                HIP_CHECK(hipStreamSynchronize(R->stream));
+                if (kth.overflow != 1 || nslots >= nslots_cap) break;
+                ps.release(d_slots);
+                d_slots = nullptr;
+                nslots *= 4;
+                if (nslots > nslots_cap) nslots = nslots_cap;
+                HIP_CHECK(hipMemsetAsync(d_kth, 0, sizeof(TableHdr), R->stream));
+            }
+            if (kth.overflow == 1) {
+                set_err(errbuf, errlen, "string key id table overflow");
+                return YT_ERR_CAPACITY;
+            }
+        }
+        const int64_t D = (int64_t)kth.ngroups;
+        StrKeyTab& T = tabs[i];
+        T.ids.resize((size_t)D);
+        if (D > 0) {
+            StrKeyId* d_ids = nullptr;
+            char* d_pool = nullptr;
+            unsigned long long* d_ctr = nullptr;
+            unsigned long long hctr[2] = {0, 0};
+            HIP_CHECK(ps.dev(&d_ids, sizeof(StrKeyId) * D));
+            HIP_CHECK(ps.dev(&d_pool, pool_cap));
+            HIP_CHECK(ps.dev(&d_ctr, 2 * sizeof(unsigned long long)));
+            HIP_CHECK(hipMemsetAsync(d_ctr, 0, 2 * sizeof(unsigned long long),
+                                     R->stream));
+            HIP_CHECK(ytql_launch_strkey_compact(R->d_segs, R->d_segex, off, d_slots,
+                                                 nslots, d_ids, d_ctr, d_pool,
+                                                 d_ctr + 1, pool_cap, d_kth,
+                                                 R->stream));
+            HIP_CHECK(ytql_launch_strkey_remap(d_slots, d_map, entries, R->stream));
+            HIP_CHECK(hipMemcpyAsync(&kth, d_kth, sizeof(kth), hipMemcpyDeviceToHost,
+                                     R->stream));
+            HIP_CHECK(hipMemcpyAsync(hctr, d_ctr, sizeof(hctr), hipMemcpyDeviceToHost,
+                                     R->stream));
+            HIP_CHECK(hipMemcpyAsync(T.ids.data(), d_ids, sizeof(StrKeyId) * D,
+                                     hipMemcpyDeviceToHost, R->stream));
+            HIP_CHECK(hipStreamSynchronize(R->stream));
+            if (kth.overflow == 1 || hctr[0] != (unsigned long long)D ||
+                hctr[1] > pool_cap) {
+                set_err(errbuf, errlen, "string key id pool overflow");
+                return YT_ERR_CAPACITY;
+            }
+            T.pool.resize((size_t)(hctr[1] ? hctr[1] : 1));
+            if (hctr[1])
+                HIP_CHECK(hipMemcpy(T.pool.data(), d_pool, (size_t)hctr[1],
+                                    hipMemcpyDeviceToHost));
+        }
+        t_last_strkey_entries += (uint64_t)entries;
+        t_last_strkey_distinct += (uint64_t)D;
+        if (timing) {
+            float ms = 0;
+            HIP_CHECK(hipEventRecord(e1, R->stream));
+            HIP_CHECK(hipEventSynchronize(e1));
+            HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+            fprintf(stderr, "[ytql timing] string key ids: %lld entries, %lld "
+                            "distinct, entry pass %.3fms\n",
+                    (long long)entries, (long long)D, ms);
+        }
+        HIP_CHECK(hipStreamSynchronize(R->stream));
+        R->strkeys.kmap[i] = d_map;
+        R->strkeys.kbase[i] = d_base;
     }
     return YT_OK;
 }
@@ -4967,6 +5217,8 @@ extern "C" int yt_gpu_query_execute(
     t_last_strpred_entries = 0;
     t_last_strjoin_inserted = 0;
     t_last_strjoin_entries = 0;
+    t_last_strkey_entries = 0;
+    t_last_strkey_distinct = 0;
     t_last_inlist_mode = 0;
     t_last_topk = 0;
     if (plan->having && expr_has_strlit(plan->having)) {
@@ -5053,6 +5305,9 @@ extern "C" int yt_gpu_query_execute(
      * any chunk that holds a non-int64 column, so this never fires; it is
      * stated so that it does not depend on that */
     if (SP.any) fs.valid = fs.ragged = 0;
+    /* so does a packed STRING key; a multi-key plan is no fast shape either */
+    for (int i = 0; i < dp.kp_count; i++)
+        if (kp_is_str(&dp, i)) fs.valid = fs.ragged = 0;
 
     DeviceRun R;
     R.stream = (hipStream_t)(uintptr_t)options->stream;
@@ -5068,14 +5323,18 @@ extern "C" int yt_gpu_query_execute(
     rc = setup_chunk(chunk, &R, &maxw, options->input_row_limit, &in_clamped,
                      errbuf, errlen);
     if (rc) return rc;
+    StrKeyTab strtabs[kMaxPackKeys];
     if (dp.kp_count && chunk->row_count > 0 && R.nsegs > 0) {
-        rc = pack_group_key(&dp, &R, errbuf, errlen);
+        rc = setup_strkey_ids(&R, &dp, strtabs, errbuf, errlen);
+        if (rc) return rc;
+        rc = pack_group_key(&dp, &R, errbuf, errlen, strtabs);
         if (rc) return rc;
     }
 
     if (chunk->row_count == 0 || R.nsegs == 0) {
         /* zero groups -> single final flush emits nothing (registry.cpp:1481) */
         output->row_count = 0;
+        output->string_pool_used = 0;
         output->column_count = plan->project_count ? plan->project_count
             : (plan->key_count + plan->agg_count);
         return YT_OK;
@@ -5163,7 +5422,8 @@ extern "C" int yt_gpu_query_execute(
         rc = emit_rows(plan, chunk, &dp, hgroups, ngroups, th, 0, gaccum.data(),
                        fs.valid && fs.key_col < 0,
                        options->output_row_limit, &out_limited,
-                       output, errbuf, errlen, hslim, hslim ? &slices : nullptr);
+                       output, errbuf, errlen, hslim, hslim ? &slices : nullptr,
+                       strtabs);
         if (hslim) {
             /* emit_rows can return before the last slice has landed */
             hipError_t es = hipStreamSynchronize(R.stream);
@@ -5227,6 +5487,16 @@ static int query_partial_impl(
         return YT_ERR_UNSUPPORTED;
     }
     if (partition_count < 1 || partition_count > 64) { set_err(errbuf, errlen, "partial: 1..64 partitions"); return YT_ERR_UNSUPPORTED; }
+    for (int i = 0; plan->key_count > 1 && i < plan->key_count; i++) {
+        int kc;
+        if (expr_is_col(plan->keys[i], &kc) && kc >= 0 && kc < chunk->column_count &&
+            chunk->columns[kc].value_type == YT_VT_STRING) {
+            set_err(errbuf, errlen,
+                    "partial: multi-key GROUP BY with a string key: string ids "
+                    "are local to one chunk and cannot be exchanged");
+            return YT_ERR_UNSUPPORTED;
+        }
+    }
     /* join at the bottom query (the reference's coordinated split keeps
      * JoinClause in the bottom, coordinator.cpp:130-170: the dimension
      * table is available on every node) — each rank builds the foreign
@@ -5265,6 +5535,8 @@ static int query_partial_impl(
     t_last_strpred_entries = 0;
     t_last_strjoin_inserted = 0;
     t_last_strjoin_entries = 0;
+    t_last_strkey_entries = 0;
+    t_last_strkey_distinct = 0;
     t_last_inlist_mode = 0;
     t_last_topk = 0;
     DevPlan dp;
@@ -5469,6 +5741,8 @@ extern "C" int yt_gpu_query_partial_str(
     t_last_strpred_entries = 0;
     t_last_strjoin_inserted = 0;
     t_last_strjoin_entries = 0;
+    t_last_strkey_entries = 0;
+    t_last_strkey_distinct = 0;
     t_last_inlist_mode = 0;
     t_last_topk = 0;
     StrPartialOut po;
@@ -5508,6 +5782,12 @@ extern "C" int yt_gpu_key_ranges(
             set_err(errbuf, errlen, "key_ranges: plain key columns only");
             return YT_ERR_UNSUPPORTED;
         }
+        if (plan->key_count > 1 && chunk->columns[c].value_type == YT_VT_STRING) {
+            set_err(errbuf, errlen,
+                    "key_ranges: multi-key GROUP BY with a string key: string "
+                    "ids are local to one chunk and cannot be exchanged");
+            return YT_ERR_UNSUPPORTED;
+        }
         key_zzmin[i] = R.col_zzmin[c];
         key_zzmax[i] = R.col_zzmax[c];
     }
@@ -5530,6 +5810,16 @@ static int merge_states_impl(
     if (plan->key_count > 1 && (!key_zzmin || !key_zzmax)) {
         set_err(errbuf, errlen, "merge: multi-key needs the common key ranges");
         return YT_ERR_UNSUPPORTED;
+    }
+    for (int i = 0; plan->key_count > 1 && col_types && i < plan->key_count; i++) {
+        int kc;
+        if (expr_is_col(plan->keys[i], &kc) && kc >= 0 && kc < kMaxCols &&
+            col_types[kc] == YT_VT_STRING) {
+            set_err(errbuf, errlen,
+                    "merge: multi-key GROUP BY with a string key: string ids "
+                    "are local to one chunk and cannot be exchanged");
+            return YT_ERR_UNSUPPORTED;
+        }
     }
     output->totals_row = 0;
     int sum_slot = -1;

@@ -840,6 +840,16 @@ __device__ __noinline__ DVal str_entry_at(const DevSeg& s, const SegEx& e, int64
     return v;
 }
 
+/* The code of a non-null STRING component of the composite group key
+ * (StrKeyDev): ref is the row's entry as str_entry_at gives it, the code is
+ * 1 + the string id of that entry (k_strkey_*). Out of line for the reason
+ * given at str_pred_row. */
+__device__ __noinline__ uint64_t strkey_code(const uint32_t* kmap, const int64_t* kbase,
+                                             uint64_t ref)
+{
+    return 1 + (uint64_t)kmap[kbase[ref >> 32] + (int64_t)(ref & 0xFFFFFFFFu)];
+}
+
 /* P_STR_REF: the row's value of a projected STRING column, as a reference to
  * its entry (common.h). Out of line for the reason given at str_pred_row. */
 __device__ __noinline__ DVal str_ref_row(const DevPlan& p, const ColCtx& c, const PInst& in)
@@ -1550,7 +1560,7 @@ k_scan_generic(DevPlan p, const DevSeg* segs, const SegEx* segex,
                const int32_t* col_seg_off, const int32_t* col_seg_cnt,
                int64_t row_count, JoinDev jd, JoinDev jd2,
                TableHdr* th, unsigned long long* slots,
-               unsigned* error_out)
+               unsigned* error_out, StrKeyDev sk)
 {
     ColCtx c;
     c.segs = segs;
@@ -1596,7 +1606,9 @@ k_scan_generic(DevPlan p, const DevSeg* segs, const SegEx* segex,
             for (int i = 0; i < p.kp_count; i++) {
                 DVal v = col_value(p, c, p.kp_col[i]);
                 uint64_t enc = 0;
-                if (!v.null_) {
+                if (!v.null_ && v.type == YT_VT_STRING) {
+                    enc = strkey_code(sk.kmap[i], sk.kbase[i], v.bits);
+                } else if (!v.null_) {
                     uint64_t z = p.kp_signed[i]
                         ? (((uint64_t)v.bits << 1)
                            ^ (uint64_t)(((int64_t)v.bits) >> 63))
@@ -3567,6 +3579,91 @@ k_strgrp_compact(const DevSeg* segs, const SegEx* segex, int key_seg_off,
 }
 
 /* ------------------------------------------------------------------ */
+/* string ids of a multi-key GROUP BY's STRING key column (common.h
+ * StrKeyId): one dense id per distinct string over the
+ * entries of the column's kept segments, so that the composite packer takes
+ * the column as one more integer component. k_strgrp_hash gives every entry
+ * its hash, ident and prefix; then
+ *   k_strkey_claim   one lane per entry: find or claim the string's slot,
+ *                    kmap[entry] = slot index
+ *   k_strkey_compact occupied slots -> ids 0..D-1 in slot order, bytes into
+ *                    the pool in id order; the id is left in the slot
+ *   k_strkey_remap   kmap[entry] = the id its slot was given
+ * Null entries exist in the direct layouts only (an entry is a row or a
+ * run there, null by the segment's bitmap): they claim nothing and keep
+ * kStrKeyNoId, which no row reads, because a null row never looks up. */
+
+__global__ void __launch_bounds__(256)
+k_strkey_claim(const DevSeg* segs, const SegEx* segex, int key_seg_off, int nsegs,
+               const int64_t* kbase, const uint64_t* hashes,
+               const uint64_t* idents, const ulonglong2* pfxs,
+               StrSlot* slots, uint64_t nslots, uint32_t* kmap, TableHdr* th)
+{
+    const int64_t total = kbase[nsegs];
+    __shared__ unsigned long long s_claims;
+    if (threadIdx.x == 0) s_claims = 0;
+    __syncthreads();
+    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         g < total; g += (int64_t)gridDim.x * blockDim.x) {
+        const int s = seg_of(kbase, nsegs, g);
+        const DevSeg& sk = segs[key_seg_off + s];
+        const SegEx& ek = segex[key_seg_off + s];
+        if ((ek.flags & (32 | 64)) &&
+            bm_get((const uint8_t*)sk.blob + ek.off_bitmap_bytes, g - kbase[s])) {
+            kmap[g] = kStrKeyNoId;
+            continue;
+        }
+        DictEntryKey<false> key(segs, segex, key_seg_off, nsegs, kbase, hashes,
+                                idents, pfxs, g);
+        bool claimed;
+        StrSlot* slot = strslot_find_or_claim(slots, nslots - 1, key, &claimed);
+        if (!slot) {
+            th->overflow = 1;
+            kmap[g] = kStrKeyNoId;
+            continue;
+        }
+        if (claimed) atomicAdd(&s_claims, 1ULL);
+        kmap[g] = (uint32_t)(slot - slots);
+    }
+    strslot_fold_claims(&s_claims, th);
+}
+
+/* id idx: the owner's claim word and where its bytes went; the slot keeps
+ * the id (sum_bits, unused by this table) for k_strkey_remap */
+struct StrKeyIdWriter {
+    StrKeyId* out;
+    StrSlot* slots;
+    __device__ __forceinline__ void write(uint64_t idx, unsigned long long off_len,
+                                          const StrSlot& sl) const
+    {
+        out[idx].off_len = off_len;
+        out[idx].rep = sl.rep;
+        slots[&sl - slots].sum_bits = idx;
+    }
+};
+
+__global__ void __launch_bounds__(256)
+k_strkey_compact(const DevSeg* segs, const SegEx* segex, int key_seg_off,
+                 StrSlot* slots, uint64_t nslots, StrKeyId* out,
+                 unsigned long long* counter, char* pool,
+                 unsigned long long* pool_cursor, uint64_t pool_cap, TableHdr* th)
+{
+    strslot_compact(slots, nslots, DictEntrySrc{segs, segex, key_seg_off},
+                    StrKeyIdWriter{out, slots}, counter, pool, pool_cursor,
+                    pool_cap, th);
+}
+
+__global__ void __launch_bounds__(256)
+k_strkey_remap(const StrSlot* slots, uint32_t* kmap, int64_t total)
+{
+    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         g < total; g += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t si = kmap[g];
+        if (si != kStrKeyNoId) kmap[g] = (uint32_t)slots[si].sum_bits;
+    }
+}
+
+/* ------------------------------------------------------------------ */
 /* general string-keyed GROUP BY (common.h StrGenAggs): any filter, the
  * whole aggregate family, all four key layouts, ragged segmentation. Same
  * three stages as the specialised kernels above — dense per-(segment,
@@ -4974,14 +5071,15 @@ hipError_t ytql_launch_scan_generic(const DevPlan* p, const DevSeg* segs,
                                     int64_t row_count, const JoinDev* jd,
                                     const JoinDev* jd2,
                                     TableHdr* th, unsigned long long* slots,
-                                    unsigned* error_out, hipStream_t st)
+                                    unsigned* error_out, const StrKeyDev* sk,
+                                    hipStream_t st)
 {
     int block = 256;
     int64_t want = (row_count + block - 1) / block;
     int grid = (int)(want > 4096 ? 4096 : (want > 0 ? want : 1));
     hipLaunchKernelGGL(k_scan_generic, dim3(grid), dim3(block), 0, st,
                        *p, segs, segex, col_seg_off, col_seg_cnt, row_count,
-                       *jd, *jd2, th, slots, error_out);
+                       *jd, *jd2, th, slots, error_out, *sk);
     return hipGetLastError();
 }
 
@@ -5092,6 +5190,48 @@ hipError_t ytql_launch_strgrp_compact(const DevSeg* segs, const SegEx* segex,
     hipLaunchKernelGGL(k_strgrp_compact, dim3(grid), dim3(256), 0, st,
                        segs, segex, key_seg_off, slots, nslots, out, counter,
                        pool, pool_cursor, pool_cap, th);
+    return hipGetLastError();
+}
+
+hipError_t ytql_launch_strkey_claim(const DevSeg* segs, const SegEx* segex,
+                                    int key_seg_off, int nsegs,
+                                    const int64_t* kbase, const uint64_t* hashes,
+                                    const uint64_t* idents, const ulonglong2* pfxs,
+                                    StrSlot* slots, uint64_t nslots,
+                                    uint32_t* kmap, TableHdr* th,
+                                    int64_t total, hipStream_t st)
+{
+    int64_t want = (total + 255) / 256;
+    int grid = (int)(want > 4096 ? 4096 : (want ? want : 1));
+    hipLaunchKernelGGL(k_strkey_claim, dim3(grid), dim3(256), 0, st,
+                       segs, segex, key_seg_off, nsegs, kbase, hashes, idents,
+                       pfxs, slots, nslots, kmap, th);
+    return hipGetLastError();
+}
+
+hipError_t ytql_launch_strkey_compact(const DevSeg* segs, const SegEx* segex,
+                                      int key_seg_off,
+                                      StrSlot* slots, uint64_t nslots,
+                                      StrKeyId* out, unsigned long long* counter,
+                                      char* pool, unsigned long long* pool_cursor,
+                                      uint64_t pool_cap, TableHdr* th,
+                                      hipStream_t st)
+{
+    uint64_t want = (nslots + 255) / 256;
+    int grid = (int)(want > 2048 ? 2048 : (want ? want : 1));
+    hipLaunchKernelGGL(k_strkey_compact, dim3(grid), dim3(256), 0, st,
+                       segs, segex, key_seg_off, slots, nslots, out, counter,
+                       pool, pool_cursor, pool_cap, th);
+    return hipGetLastError();
+}
+
+hipError_t ytql_launch_strkey_remap(const StrSlot* slots, uint32_t* kmap,
+                                    int64_t total, hipStream_t st)
+{
+    int64_t want = (total + 255) / 256;
+    int grid = (int)(want > 4096 ? 4096 : (want ? want : 1));
+    hipLaunchKernelGGL(k_strkey_remap, dim3(grid), dim3(256), 0, st,
+                       slots, kmap, total);
     return hipGetLastError();
 }
 

@@ -99,7 +99,8 @@ hipError_t ytql_launch_str_gather(const ytql::DevSeg*, const ytql::SegEx*,
 hipError_t ytql_launch_scan_generic(const ytql::DevPlan*, const ytql::DevSeg*, const ytql::SegEx*,
                                     const int32_t*, const int32_t*, int64_t,
                                     const ytql::JoinDev*, const ytql::JoinDev*,
-                                    ytql::TableHdr*, unsigned long long*, unsigned*, hipStream_t);
+                                    ytql::TableHdr*, unsigned long long*, unsigned*,
+                                    const ytql::StrKeyDev*, hipStream_t);
 hipError_t ytql_launch_scan_fast(const ytql::FastParams*, const ytql::DevSeg*, const ytql::SegEx*,
                                  const ytql::FastCol*, ytql::TableHdr*, unsigned long long*,
                                  unsigned long long*, size_t, int, hipStream_t);
@@ -128,6 +129,16 @@ hipError_t ytql_launch_strgrp_compact(const ytql::DevSeg*, const ytql::SegEx*, i
                                       const ytql::StrSlot*, uint64_t, ytql::OutStrGroup*,
                                       unsigned long long*, char*, unsigned long long*,
                                       uint64_t, ytql::TableHdr*, hipStream_t);
+hipError_t ytql_launch_strkey_claim(const ytql::DevSeg*, const ytql::SegEx*, int, int,
+                                    const int64_t*, const uint64_t*, const uint64_t*,
+                                    const ulonglong2*, ytql::StrSlot*, uint64_t,
+                                    uint32_t*, ytql::TableHdr*, int64_t, hipStream_t);
+hipError_t ytql_launch_strkey_compact(const ytql::DevSeg*, const ytql::SegEx*, int,
+                                      ytql::StrSlot*, uint64_t, ytql::StrKeyId*,
+                                      unsigned long long*, char*, unsigned long long*,
+                                      uint64_t, ytql::TableHdr*, hipStream_t);
+hipError_t ytql_launch_strkey_remap(const ytql::StrSlot*, uint32_t*, int64_t,
+                                    hipStream_t);
 hipError_t ytql_launch_strpred_entries(const ytql::DevSeg*, const ytql::SegEx*, int, int,
                                        const int64_t*, int64_t, int, int,
                                        const char*, int64_t, uint64_t*,
