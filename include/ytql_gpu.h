@@ -222,6 +222,46 @@ enum {
  * codes are local to one chunk and cannot be exchanged). One STRING key
  * alone keeps its own path (YT_SCAN_PATH_STR_DENSE / _STR_GENERAL). */
 
+/* Expression typing (GPU entries and the CPU oracle alike). Types are static:
+ * they follow from the plan and the column types, never from a row, and a
+ * plan that breaks a rule is refused before anything runs.
+ *   - The static type of a node: a column's type; INT64 for YT_EX_LIT_I64,
+ *     DOUBLE for YT_EX_LIT_DOUBLE, NULL for YT_EX_LIT_NULL; BOOLEAN for the
+ *     comparisons, AND, OR, NOT and IN. An arithmetic node has the common type
+ *     of its operands after the rules below, not the type of `a`: a null
+ *     operand leaves the other one's type (null + <double column> is DOUBLE).
+ *     Aggregate state and result types, IN operand typing and rowset column
+ *     types all follow this type.
+ *   - A YT_EX_LIT_I64 operand of an arithmetic or relational node adopts the
+ *     other operand's static type: beside DOUBLE it is that integer converted
+ *     to double (<double column> > 5 compares with 5.0); beside UINT64 it is
+ *     read as UINT64, and a negative one is YT_ERR_INVALID_PLAN "type
+ *     mismatch"; beside INT64, BOOLEAN or NULL it stays INT64. A
+ *     YT_EX_LIT_DOUBLE is never converted.
+ *   - After adoption, YT_ERR_INVALID_PLAN "type mismatch" when one operand of
+ *     an arithmetic or relational node is DOUBLE and the other neither DOUBLE
+ *     nor NULL, or one is INT64 and the other UINT64. Nothing converts a
+ *     column: write <int column> + <double column> with explicit same-typed
+ *     operands. MOD with a DOUBLE operand is YT_ERR_UNSUPPORTED.
+ *   - BOOLEAN beside INT64 or UINT64 is legal, and the left operand's type
+ *     decides how both 64-bit patterns are read (signed for INT64, unsigned
+ *     for UINT64 and BOOLEAN). AND, OR, NOT and a filter's or HAVING's truth
+ *     value take any non-null operand: non-zero is true.
+ *   - Values: integers wrap mod 2^64; DIV truncates toward zero and MOD takes
+ *     the dividend's sign, INT64_MIN / -1 = INT64_MIN, INT64_MIN % -1 = 0; an
+ *     integer zero divisor on a row that passes the filter is
+ *     YT_ERR_DIV_ZERO (a null operand gives null before the divisor is looked
+ *     at). Comparisons never give null: null sorts below every value and
+ *     equals null; any NaN operand makes all six true. AND and OR are Kleene,
+ *     NOT of null is null.
+ * Limits of the device interpreter (GPU entries): an expression may need at
+ * most 12 evaluation stack slots, where a leaf needs 1, NOT and IN what their
+ * operand needs, and a binary node max(need(a), 1 + need(b)); a left-deep
+ * chain a + b + c + ... needs 2, the right-nested a + (b + (c + ...)) one per
+ * leaf. A deeper one is YT_ERR_UNSUPPORTED. All expressions of a plan
+ * together compile to at most 48 instructions (one per node); more is
+ * YT_ERR_INVALID_PLAN "expression too long". */
+
 typedef struct YtExpr {
     int32_t op;           /* YT_EX_* */
     int32_t col;          /* for YT_EX_COLUMN */

@@ -319,6 +319,156 @@ typedef struct {
 
 static Val VNULL(void) { Val v; v.type = YT_VT_NULL; v.bits = 0; v.str = 0; v.len = 0; return v; }
 
+/* ---- expression typing (include/ytql_gpu.h, comment above YtExpr) ----
+ * The oracle's own statement of the rules; it shares no code with the GPU
+ * library. type_expr gives the static type of a tree and refuses what the
+ * rules refuse; yto_execute runs it over every expression of a plan before
+ * it decodes a column. */
+
+static int op_is_arith(int op) { return op >= YT_EX_ADD && op <= YT_EX_MOD; }
+static int op_is_rel(int op) { return op >= YT_EX_EQ && op <= YT_EX_GE; }
+
+/* the type an operand node has beside an operand of type `other`: an integer
+ * literal takes the type of a DOUBLE or UINT64 neighbour */
+static int type_adopt(const YtExpr* e, uint8_t own, uint8_t other, uint8_t* out,
+                      char* errbuf, size_t errlen)
+{
+    *out = own;
+    if (e->op != YT_EX_LIT_I64) return YT_OK;
+    if (other == YT_VT_DOUBLE) *out = YT_VT_DOUBLE;
+    if (other == YT_VT_UINT64) {
+        if (e->lit_i64 < 0) {
+            set_err(errbuf, errlen,
+                    "type mismatch: negative integer literal beside a uint64 operand");
+            return YT_ERR_INVALID_PLAN;
+        }
+        *out = YT_VT_UINT64;
+    }
+    return YT_OK;
+}
+
+static int type_expr(const YtExpr* e, const uint8_t* types, int ncols,
+                     uint8_t* out, char* errbuf, size_t errlen)
+{
+    if (!e) { set_err(errbuf, errlen, "null expr"); return YT_ERR_INVALID_PLAN; }
+    switch (e->op) {
+    case YT_EX_COLUMN:
+        if (e->col < 0 || e->col >= ncols) {
+            set_err(errbuf, errlen, "column index out of range");
+            return YT_ERR_INVALID_PLAN;
+        }
+        *out = types[e->col];
+        return YT_OK;
+    case YT_EX_LIT_I64: *out = YT_VT_INT64; return YT_OK;
+    case YT_EX_LIT_DOUBLE: *out = YT_VT_DOUBLE; return YT_OK;
+    case YT_EX_LIT_NULL: *out = YT_VT_NULL; return YT_OK;
+    case YT_EX_NOT: {
+        uint8_t t;
+        int rc = type_expr(e->a, types, ncols, &t, errbuf, errlen);
+        *out = YT_VT_BOOLEAN;
+        return rc;
+    }
+    default:
+        break;
+    }
+    int logical = e->op == YT_EX_AND || e->op == YT_EX_OR;
+    if (!logical && !op_is_arith(e->op) && !op_is_rel(e->op)) {
+        set_err(errbuf, errlen, "oracle: unknown expression node");
+        return YT_ERR_UNSUPPORTED;
+    }
+    uint8_t ta, tb;
+    int rc = type_expr(e->a, types, ncols, &ta, errbuf, errlen);
+    if (rc != YT_OK) return rc;
+    rc = type_expr(e->b, types, ncols, &tb, errbuf, errlen);
+    if (rc != YT_OK) return rc;
+    *out = YT_VT_BOOLEAN;
+    if (logical) return YT_OK;
+    uint8_t xa, xb;
+    rc = type_adopt(e->a, ta, tb, &xa, errbuf, errlen);
+    if (rc != YT_OK) return rc;
+    rc = type_adopt(e->b, tb, ta, &xb, errbuf, errlen);
+    if (rc != YT_OK) return rc;
+    if ((xa == YT_VT_DOUBLE && xb != YT_VT_DOUBLE && xb != YT_VT_NULL) ||
+        (xb == YT_VT_DOUBLE && xa != YT_VT_DOUBLE && xa != YT_VT_NULL)) {
+        set_err(errbuf, errlen,
+                "type mismatch: a double operand beside an operand that is not double");
+        return YT_ERR_INVALID_PLAN;
+    }
+    if ((xa == YT_VT_INT64 && xb == YT_VT_UINT64) ||
+        (xa == YT_VT_UINT64 && xb == YT_VT_INT64)) {
+        set_err(errbuf, errlen, "type mismatch: int64 operand beside a uint64 operand");
+        return YT_ERR_INVALID_PLAN;
+    }
+    if (op_is_rel(e->op)) return YT_OK;
+    /* arithmetic: a null operand leaves the other one's type; boolean beside
+     * an integer keeps the left one's */
+    *out = xa == YT_VT_NULL ? xb : xa;
+    if (e->op == YT_EX_MOD && *out == YT_VT_DOUBLE) {
+        set_err(errbuf, errlen, "modulo over double operands: unsupported");
+        return YT_ERR_UNSUPPORTED;
+    }
+    return YT_OK;
+}
+
+/* every expression of the plan against the (joined) input column types */
+static int type_plan(const YtPlan* plan, const uint8_t* types, int ncols,
+                     char* errbuf, size_t errlen)
+{
+    uint8_t t, row[32];
+    int rc, nrow = 0;
+    if (plan->filter) {
+        rc = type_expr(plan->filter, types, ncols, &t, errbuf, errlen);
+        if (rc != YT_OK) return rc;
+    }
+    if (plan->key_count + plan->agg_count > 32) {
+        set_err(errbuf, errlen, "too many output columns");
+        return YT_ERR_UNSUPPORTED;
+    }
+    for (int k = 0; k < plan->key_count; k++) {
+        rc = type_expr(plan->keys[k], types, ncols, &row[nrow++], errbuf, errlen);
+        if (rc != YT_OK) return rc;
+    }
+    for (int a = 0; a < plan->agg_count; a++) {
+        int f = plan->aggs[a]->func;
+        t = YT_VT_INT64;                       /* sum(1), the count leg */
+        if (f != YT_AGG_SUM1) {
+            rc = type_expr(plan->aggs[a]->arg, types, ncols, &t, errbuf, errlen);
+            if (rc != YT_OK) return rc;
+        }
+        if (f == YT_AGG_AVG) t = YT_VT_DOUBLE;
+        if (f == YTO_AGG_NNCNT) t = YT_VT_INT64;
+        row[nrow++] = t;
+    }
+    /* a grouped plan's projections and HAVING read the rows [keys, aggs] */
+    int grouped = plan->agg_count > 0 || plan->key_count > 0;
+    for (int p = 0; p < plan->project_count; p++) {
+        rc = type_expr(plan->projects[p], grouped ? row : types,
+                       grouped ? nrow : ncols, &t, errbuf, errlen);
+        if (rc != YT_OK) return rc;
+    }
+    if (plan->having && grouped) {
+        rc = type_expr(plan->having, row, nrow, &t, errbuf, errlen);
+        if (rc != YT_OK) return rc;
+    }
+    return YT_OK;
+}
+
+/* The value of an operand beside the value `other`. type_plan has passed, so
+ * a non-null value has its node's static type and reading the neighbour's
+ * type off its value decides as the static rule does; beside a null
+ * neighbour the literal's type changes nothing. */
+static void val_adopt(const YtExpr* e, Val* v, const Val* other)
+{
+    if (e->op != YT_EX_LIT_I64) return;
+    if (other->type == YT_VT_DOUBLE) {
+        double d = (double)e->lit_i64;
+        v->type = YT_VT_DOUBLE;
+        memcpy(&v->bits, &d, 8);
+    } else if (other->type == YT_VT_UINT64) {
+        v->type = YT_VT_UINT64;
+    }
+}
+
 static Val eval_expr(const YtExpr* e, EvalCtx* ctx)
 {
     Val v = VNULL();
@@ -364,6 +514,10 @@ static Val eval_expr(const YtExpr* e, EvalCtx* ctx)
 
     Val a = eval_expr(e->a, ctx);
     Val b = eval_expr(e->b, ctx);
+    if (op_is_arith(e->op) || op_is_rel(e->op)) {
+        val_adopt(e->a, &a, &b);
+        val_adopt(e->b, &b, &a);
+    }
 
     if (e->op >= YT_EX_ADD && e->op <= YT_EX_MOD) {
         /* arithmetic: null-propagating (cg_fragment_compiler.cpp arithmetic op) */
@@ -1112,6 +1266,23 @@ int yto_execute(const YtPlan* plan, const YtChunk* chunk,
         return YT_ERR_UNSUPPORTED;
     }
     int ncols_eff = ncols + jF + jF2;
+    {
+        /* expression typing over [primary columns, joined foreign columns],
+         * before anything is decoded */
+        uint8_t st[64];
+        int nst = 0;
+        if (ncols_eff > 64) {
+            set_err(errbuf, errlen, "too many columns");
+            return YT_ERR_UNSUPPORTED;
+        }
+        for (int c = 0; c < ncols; c++)
+            st[nst++] = (uint8_t)chunk->columns[c].value_type;
+        for (const YtJoin* J = plan->join; J; J = J->next)
+            for (int j = 0; j < J->foreign_value_count; j++)
+                st[nst++] = (uint8_t)J->foreign->columns[J->foreign_value_cols[j]].value_type;
+        int trc = type_plan(plan, st, nst, errbuf, errlen);
+        if (trc != YT_OK) return trc;
+    }
     uint8_t* jdrop = NULL;
     int64_t n = chunk->row_count;
     int64_t n_scan = chunk->row_count;   /* expanded row count under dup joins */

@@ -42,6 +42,9 @@ struct SegEx {
  * (cg_fragment_compiler.cpp arithmetic/relational/logical codegen). */
 enum POp : int32_t {
     P_COL = 0, P_LIT_I64 = 1, P_LIT_NULL = 2, P_LIT_DOUBLE = 3,
+    /* a YT_EX_LIT_I64 that faces a UINT64 operand (include/ytql_gpu.h,
+     * expression typing): the same bits, typed UINT64. No YT_EX_* node. */
+    P_LIT_U64 = 5,
     P_ADD = 10, P_SUB = 11, P_MUL = 12, P_DIV = 13, P_MOD = 14,
     P_EQ = 20, P_NE = 21, P_LT = 22, P_LE = 23, P_GT = 24, P_GE = 25,
     P_AND = 30, P_OR = 31, P_NOT = 32,
@@ -77,6 +80,10 @@ struct PInst {
 };
 
 constexpr int kMaxProg = 48;
+/* slots of eval_prog's value stack. A leaf needs 1, NOT and IN what their
+ * operand needs, a binary node max(need(a), 1 + need(b)): compile_expr
+ * refuses a program that needs more, so no thread indexes past the array. */
+constexpr int kEvalStack = 12;
 constexpr int kMaxCols = 8;
 constexpr int kMaxAggs = 4;
 constexpr int kMaxStrPreds = 4;    /* string predicates with a bitmap per filter */

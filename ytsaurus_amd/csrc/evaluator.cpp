@@ -255,12 +255,47 @@ extern "C" int yt_gpu_available(char* errbuf, size_t errlen)
 
 struct StrPreds;
 static int compile_in_num(const YtExpr* e, DevPlan* p, StrPreds* sp, int* len,
-                          char* errbuf, size_t errlen);
+                          char* errbuf, size_t errlen, int* need);
 
+/* ---- expression typing (include/ytql_gpu.h, the comment above YtExpr) ----
+ * Decided from static types, before any kernel runs: check_plan_types
+ * refuses what the rules refuse, compile_expr emits an adopting integer
+ * literal in its adopted type, and expr_static_type gives an arithmetic
+ * node the common type of its operands. */
+
+static inline bool op_is_arith(int op) { return op >= YT_EX_ADD && op <= YT_EX_MOD; }
+static inline bool op_is_rel(int op) { return op >= YT_EX_EQ && op <= YT_EX_GE; }
+
+/* the type operand e, of static type `own`, has beside an operand of static
+ * type `other`: an integer literal takes a DOUBLE or UINT64 neighbour's */
+static inline uint8_t adopt_type(const YtExpr* e, uint8_t own, uint8_t other)
+{
+    if (e->op == YT_EX_LIT_I64 && (other == YT_VT_DOUBLE || other == YT_VT_UINT64))
+        return other;
+    return own;
+}
+
+static uint8_t expr_static_type(const YtExpr* e, const uint8_t* col_types);
+
+/* The device stack one more operand takes: a binary node evaluates a, keeps
+ * its value and evaluates b. */
+static int need_check(int need, char* errbuf, size_t errlen)
+{
+    if (need <= kEvalStack) return YT_OK;
+    if (errbuf && errlen)
+        snprintf(errbuf, errlen,
+                 "expression nested too deep: it needs %d evaluation stack "
+                 "slots, the limit is %d", need, kEvalStack);
+    return YT_ERR_UNSUPPORTED;
+}
+
+/* *need (optional) = the evaluation stack slots the program of e takes; a
+ * program over kEvalStack is refused at the node that exceeds it */
 static int compile_expr(const YtExpr* e, DevPlan* p, StrPreds* sp, int* len,
-                        char* errbuf, size_t errlen)
+                        char* errbuf, size_t errlen, int* need = nullptr)
 {
     if (!e) { set_err(errbuf, errlen, "null expr"); return YT_ERR_INVALID_PLAN; }
+    int need_here = 1;
     switch (e->op) {
     case YT_EX_COLUMN:
     case YT_EX_LIT_I64:
@@ -269,21 +304,55 @@ static int compile_expr(const YtExpr* e, DevPlan* p, StrPreds* sp, int* len,
         break;
     case YT_EX_IN:
         /* one operand and a literal list: the operand, then P_IN_NUM */
-        return compile_in_num(e, p, sp, len, errbuf, errlen);
+        return compile_in_num(e, p, sp, len, errbuf, errlen, need);
     case YT_EX_NOT: {
-        int rc = compile_expr(e->a, p, sp, len, errbuf, errlen);
+        int rc = compile_expr(e->a, p, sp, len, errbuf, errlen, &need_here);
         if (rc) return rc;
         break;
     }
     default: {
-        int rc = compile_expr(e->a, p, sp, len, errbuf, errlen);
+        int na = 1, nb = 1;
+        int rc = compile_expr(e->a, p, sp, len, errbuf, errlen, &na);
         if (rc) return rc;
-        rc = compile_expr(e->b, p, sp, len, errbuf, errlen);
+        const int ia = p->prog_len - 1;
+        rc = compile_expr(e->b, p, sp, len, errbuf, errlen, &nb);
         if (rc) return rc;
+        const int ib = p->prog_len - 1;
+        need_here = std::max(na, 1 + nb);
+        rc = need_check(need_here, errbuf, errlen);
+        if (rc) return rc;
+        if (op_is_arith(e->op) || op_is_rel(e->op)) {
+            /* an integer literal operand is the one instruction just
+             * emitted for it: retype it beside a DOUBLE or UINT64 operand
+             * (check_plan_types has refused a negative one beside UINT64) */
+            const uint8_t ta = expr_static_type(e->a, p->col_types);
+            const uint8_t tb = expr_static_type(e->b, p->col_types);
+            const YtExpr* side[2] = {e->a, e->b};
+            const uint8_t to[2] = {adopt_type(e->a, ta, tb), adopt_type(e->b, tb, ta)};
+            const int at[2] = {ia, ib};
+            for (int s = 0; s < 2; s++) {
+                if (side[s]->op != YT_EX_LIT_I64) continue;
+                PInst& li = p->prog[at[s]];
+                if (to[s] == YT_VT_DOUBLE) {
+                    const double d = (double)side[s]->lit_i64;
+                    li.op = P_LIT_DOUBLE;
+                    memcpy(&li.bits, &d, 8);
+                } else if (to[s] == YT_VT_UINT64) {
+                    li.op = P_LIT_U64;
+                }
+            }
+        }
         break;
     }
     }
-    if (p->prog_len >= kMaxProg) { set_err(errbuf, errlen, "expression too long"); return YT_ERR_INVALID_PLAN; }
+    if (need) *need = need_here;
+    if (p->prog_len >= kMaxProg) {
+        if (errbuf && errlen)
+            snprintf(errbuf, errlen,
+                     "expression too long: a plan's programs hold at most %d "
+                     "instructions", kMaxProg);
+        return YT_ERR_INVALID_PLAN;
+    }
     PInst& in = p->prog[p->prog_len++];
     in.op = e->op;     /* YT_EX_* values coincide with P_* by construction */
     in.col = e->col;
@@ -298,7 +367,10 @@ static int compile_expr(const YtExpr* e, DevPlan* p, StrPreds* sp, int* len,
     return YT_OK;
 }
 
-/* static result type of an expression (for output formatting) */
+/* static result type of an expression: aggregate state and output types, IN
+ * operand typing, rowset column types. An arithmetic node has the common
+ * type of its operands after literal adoption: a null operand leaves the
+ * other one's type, BOOLEAN beside an integer keeps the left one's. */
 static uint8_t expr_static_type(const YtExpr* e, const uint8_t* col_types)
 {
     switch (e->op) {
@@ -306,12 +378,123 @@ static uint8_t expr_static_type(const YtExpr* e, const uint8_t* col_types)
     case YT_EX_LIT_I64: return YT_VT_INT64;
     case YT_EX_LIT_DOUBLE: return YT_VT_DOUBLE;
     case YT_EX_LIT_NULL: return YT_VT_NULL;
+    case YT_EX_LIT_STRING: return YT_VT_STRING;
     case YT_EX_NOT: return YT_VT_BOOLEAN;
     case YT_EX_IN: return YT_VT_BOOLEAN;
-    default:
+    default: {
         if (e->op >= YT_EX_EQ) return YT_VT_BOOLEAN;   /* cmp / and / or */
-        return expr_static_type(e->a, col_types);      /* arithmetic */
+        const uint8_t ta = expr_static_type(e->a, col_types);
+        const uint8_t tb = expr_static_type(e->b, col_types);
+        const uint8_t xa = adopt_type(e->a, ta, tb);
+        return xa == YT_VT_NULL ? adopt_type(e->b, tb, ta) : xa;
     }
+    }
+}
+
+/* Refuses a tree that breaks the typing rules; types[0..ntypes) are the
+ * static types of the columns it reads. Strings keep their own rules
+ * (compile_filter): a node with a STRING operand passes here. */
+static int check_expr_types(const YtExpr* e, const uint8_t* types, int ntypes,
+                            char* errbuf, size_t errlen)
+{
+    if (!e) { set_err(errbuf, errlen, "null expr"); return YT_ERR_INVALID_PLAN; }
+    switch (e->op) {
+    case YT_EX_COLUMN:
+        if (e->col < 0 || e->col >= ntypes) {
+            set_err(errbuf, errlen, "column index out of range");
+            return YT_ERR_INVALID_PLAN;
+        }
+        return YT_OK;
+    case YT_EX_LIT_I64:
+    case YT_EX_LIT_DOUBLE:
+    case YT_EX_LIT_NULL:
+    case YT_EX_LIT_STRING:
+        return YT_OK;
+    case YT_EX_NOT:
+    case YT_EX_IN:                  /* one operand; the list has its own check */
+        return check_expr_types(e->a, types, ntypes, errbuf, errlen);
+    default:
+        break;
+    }
+    int rc = check_expr_types(e->a, types, ntypes, errbuf, errlen);
+    if (rc) return rc;
+    rc = check_expr_types(e->b, types, ntypes, errbuf, errlen);
+    if (rc) return rc;
+    if (!op_is_arith(e->op) && !op_is_rel(e->op)) return YT_OK;
+    const uint8_t ta = expr_static_type(e->a, types);
+    const uint8_t tb = expr_static_type(e->b, types);
+    if (ta == YT_VT_STRING || tb == YT_VT_STRING) return YT_OK;
+    const uint8_t xa = adopt_type(e->a, ta, tb), xb = adopt_type(e->b, tb, ta);
+    for (const YtExpr* s : {e->a, e->b}) {
+        if (s->op == YT_EX_LIT_I64 && s->lit_i64 < 0 &&
+            (s == e->a ? xa : xb) == YT_VT_UINT64) {
+            set_err(errbuf, errlen,
+                    "type mismatch: a negative integer literal beside a "
+                    "UINT64 operand");
+            return YT_ERR_INVALID_PLAN;
+        }
+    }
+    if ((xa == YT_VT_DOUBLE && xb != YT_VT_DOUBLE && xb != YT_VT_NULL) ||
+        (xb == YT_VT_DOUBLE && xa != YT_VT_DOUBLE && xa != YT_VT_NULL)) {
+        set_err(errbuf, errlen,
+                "type mismatch: a DOUBLE operand beside one that is neither "
+                "DOUBLE nor null (litf() writes a double literal)");
+        return YT_ERR_INVALID_PLAN;
+    }
+    if ((xa == YT_VT_INT64 && xb == YT_VT_UINT64) ||
+        (xa == YT_VT_UINT64 && xb == YT_VT_INT64)) {
+        set_err(errbuf, errlen,
+                "type mismatch: an INT64 operand beside a UINT64 operand");
+        return YT_ERR_INVALID_PLAN;
+    }
+    if (e->op == YT_EX_MOD && (xa == YT_VT_DOUBLE || xb == YT_VT_DOUBLE)) {
+        set_err(errbuf, errlen, "modulo over DOUBLE operands: unsupported");
+        return YT_ERR_UNSUPPORTED;
+    }
+    return YT_OK;
+}
+
+/* Every expression of the plan: filter, keys, aggregate arguments and a plain
+ * scan's projections against the input column types, a grouped plan's
+ * projections and HAVING against the types of its rows [keys, aggregates]. */
+static int check_plan_types(const YtPlan* plan, const uint8_t* col_types, int ncols,
+                            char* errbuf, size_t errlen)
+{
+    int rc;
+    if (plan->filter) {
+        rc = check_expr_types(plan->filter, col_types, ncols, errbuf, errlen);
+        if (rc) return rc;
+    }
+    uint8_t row[kMaxPackKeys + kMaxAggs];
+    int nrow = 0;
+    const bool grouped = plan->key_count > 0 || plan->agg_count > 0;
+    if (plan->key_count > kMaxPackKeys || plan->agg_count > kMaxAggs)
+        return YT_OK;               /* refused by the entry that compiles it */
+    for (int k = 0; k < plan->key_count; k++) {
+        rc = check_expr_types(plan->keys[k], col_types, ncols, errbuf, errlen);
+        if (rc) return rc;
+        row[nrow++] = expr_static_type(plan->keys[k], col_types);
+    }
+    for (int a = 0; a < plan->agg_count; a++) {
+        const int f = plan->aggs[a]->func;
+        uint8_t t = YT_VT_INT64;
+        if (f != YT_AGG_SUM1) {
+            rc = check_expr_types(plan->aggs[a]->arg, col_types, ncols, errbuf, errlen);
+            if (rc) return rc;
+            t = expr_static_type(plan->aggs[a]->arg, col_types);
+        }
+        row[nrow++] = f == YT_AGG_AVG ? (uint8_t)YT_VT_DOUBLE : t;
+    }
+    for (int pj = 0; pj < plan->project_count; pj++) {
+        rc = check_expr_types(plan->projects[pj], grouped ? row : col_types,
+                              grouped ? nrow : ncols, errbuf, errlen);
+        if (rc) return rc;
+    }
+    if (plan->having && grouped) {
+        rc = check_expr_types(plan->having, row, nrow, errbuf, errlen);
+        if (rc) return rc;
+    }
+    return YT_OK;
 }
 
 static bool expr_is_col(const YtExpr* e, int* col);
@@ -501,9 +684,10 @@ static int emit_inst(DevPlan* p, int op, int col, uint64_t bits,
     return YT_OK;
 }
 
-/* numeric YT_EX_IN: the operand's program, then one P_IN_NUM */
+/* numeric YT_EX_IN: the operand's program, then one P_IN_NUM, which answers
+ * in the operand's stack slot */
 static int compile_in_num(const YtExpr* e, DevPlan* p, StrPreds* sp, int* len,
-                          char* errbuf, size_t errlen)
+                          char* errbuf, size_t errlen, int* need)
 {
     int rc = in_list_shape(e, errbuf, errlen);
     if (rc) return rc;
@@ -537,7 +721,7 @@ static int compile_in_num(const YtExpr* e, DevPlan* p, StrPreds* sp, int* len,
     const int idx = sp->in_count++;
     rc = in_num_prepare(e, vt, &sp->in[idx], errbuf, errlen);
     if (rc) return rc;
-    rc = compile_expr(e->a, p, sp, len, errbuf, errlen);
+    rc = compile_expr(e->a, p, sp, len, errbuf, errlen, need);
     if (rc) return rc;
     rc = emit_inst(p, P_IN_NUM, 0,
                    (uint64_t)idx | (sp->in[idx].has_null ? kInNullRes : 0),
@@ -865,18 +1049,25 @@ static int compile_str_leaf(const YtExpr* e, DevPlan* p, StrPreds* sp,
 /* the filter: AND/OR/NOT over string-predicate leaves and ordinary
  * subexpressions; sp == nullptr refuses every string predicate */
 static int compile_filter(const YtExpr* e, DevPlan* p, StrPreds* sp,
-                          char* errbuf, size_t errlen)
+                          char* errbuf, size_t errlen, int* need = nullptr)
 {
     if (!e) { set_err(errbuf, errlen, "null expr"); return YT_ERR_INVALID_PLAN; }
     if (e->op == YT_EX_AND || e->op == YT_EX_OR || e->op == YT_EX_NOT) {
-        int rc = compile_filter(e->a, p, sp, errbuf, errlen);
+        /* stack slots as in compile_expr */
+        int na = 1, nb = 0;
+        int rc = compile_filter(e->a, p, sp, errbuf, errlen, &na);
         if (rc) return rc;
         if (e->op != YT_EX_NOT) {
-            rc = compile_filter(e->b, p, sp, errbuf, errlen);
+            rc = compile_filter(e->b, p, sp, errbuf, errlen, &nb);
+            if (rc) return rc;
+            na = std::max(na, 1 + nb);
+            rc = need_check(na, errbuf, errlen);
             if (rc) return rc;
         }
+        if (need) *need = na;
         return emit_inst(p, e->op, e->col, 0, errbuf, errlen);
     }
+    if (need) *need = 1;            /* a string-predicate leaf pushes one value */
     if (sp) {
         int matched = 0;
         int rc = compile_str_leaf(e, p, sp, &matched, errbuf, errlen);
@@ -896,7 +1087,7 @@ static int compile_filter(const YtExpr* e, DevPlan* p, StrPreds* sp,
         return YT_ERR_UNSUPPORTED;
     }
     int len = 0;
-    return compile_expr(e, p, sp, &len, errbuf, errlen);
+    return compile_expr(e, p, sp, &len, errbuf, errlen, need);
 }
 
 static int build_devplan(const YtPlan* plan, const YtChunk* chunk, DevPlan* p,
@@ -915,6 +1106,11 @@ static int build_devplan(const YtPlan* plan, const YtChunk* chunk, DevPlan* p,
             for (int j = 0; j < J->foreign_value_count; j++)
                 p->col_types[at++] =
                     (uint8_t)J->foreign->columns[J->foreign_value_cols[j]].value_type;
+    }
+    {
+        /* the typing rules, before anything is compiled or launched */
+        int trc = check_plan_types(plan, p->col_types, p->ncols, errbuf, errlen);
+        if (trc) return trc;
     }
     for (int c = 0; c < chunk->column_count; c++) {
         const YtColumn& col = chunk->columns[c];
@@ -1322,6 +1518,23 @@ static int heval_in(const YtExpr* e, const HVal* row, int nrow, HVal* out)
     return YT_OK;
 }
 
+/* An integer literal operand beside the value `other`: the adoption
+ * compile_expr does from static types. check_plan_types has passed, so a
+ * non-null value has its node's static type, and reading the neighbour's type
+ * off its value decides the same; beside a null neighbour the literal's type
+ * changes no result. */
+static inline void hval_adopt(const YtExpr* e, HVal* v, const HVal& other)
+{
+    if (e->op != YT_EX_LIT_I64) return;
+    if (other.type == YT_VT_DOUBLE) {
+        const double d = (double)e->lit_i64;
+        v->type = YT_VT_DOUBLE;
+        memcpy(&v->bits, &d, 8);
+    } else if (other.type == YT_VT_UINT64) {
+        v->type = YT_VT_UINT64;
+    }
+}
+
 static int heval(const YtExpr* e, const HVal* row, int nrow, HVal* out)
 {
     switch (e->op) {
@@ -1349,6 +1562,10 @@ static int heval(const YtExpr* e, const HVal* row, int nrow, HVal* out)
     if (rc) return rc;
     rc = heval(e->b, row, nrow, &b);
     if (rc) return rc;
+    if (op_is_arith(e->op) || op_is_rel(e->op)) {
+        hval_adopt(e->a, &a, b);
+        hval_adopt(e->b, &b, a);
+    }
     out->type = YT_VT_NULL; out->bits = 0;
     if (e->op >= YT_EX_ADD && e->op <= YT_EX_MOD) {
         if (a.type == YT_VT_NULL || b.type == YT_VT_NULL) return YT_OK;
@@ -4588,6 +4805,12 @@ static int run_string_group(const YtPlan* plan, const YtChunk* chunk,
                 return YT_ERR_UNSUPPORTED;
             }
         }
+    } else {
+        /* no program to compile; HAVING still runs on the host */
+        rc = check_plan_types(plan, sh.col_types,
+                              std::min(chunk->column_count, kMaxCols),
+                              errbuf, errlen);
+        if (rc) return rc;
     }
     t_last_scan_path = general ? YT_SCAN_PATH_STR_GENERAL : YT_SCAN_PATH_STR_DENSE;
 
@@ -5820,6 +6043,12 @@ static int merge_states_impl(
                     "are local to one chunk and cannot be exchanged");
             return YT_ERR_UNSUPPORTED;
         }
+    }
+    if (col_types && plan->agg_count <= kMaxAggs) {
+        /* the front query evaluates HAVING and projections on the host; the
+         * typing rules need the bottom query's column types */
+        rc = check_plan_types(plan, col_types, kMaxCols, errbuf, errlen);
+        if (rc) return rc;
     }
     output->totals_row = 0;
     int sum_slot = -1;

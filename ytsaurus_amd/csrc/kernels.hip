@@ -895,7 +895,8 @@ __device__ __noinline__ void in_num_row(const DevPlan& p, const PInst& in, DVal&
 
 __device__ DVal eval_prog(const DevPlan& p, ColCtx& c, int off, int len)
 {
-    DVal stk[12];
+    /* the host refuses a program that needs more slots (compile_expr) */
+    DVal stk[kEvalStack];
     int sp = 0;
     for (int i = 0; i < len; i++) {
         const PInst& in = p.prog[off + i];
@@ -903,8 +904,10 @@ __device__ DVal eval_prog(const DevPlan& p, ColCtx& c, int off, int len)
         case P_COL:
             stk[sp++] = col_value(p, c, in.col);
             break;
-        case P_LIT_I64: {
-            DVal v; v.bits = in.bits; v.type = YT_VT_INT64; v.null_ = 0;
+        case P_LIT_I64:
+        case P_LIT_U64: {
+            DVal v; v.bits = in.bits; v.null_ = 0;
+            v.type = in.op == P_LIT_I64 ? YT_VT_INT64 : YT_VT_UINT64;
             stk[sp++] = v;
             break;
         }
